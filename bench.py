@@ -1,6 +1,13 @@
 """Headline benchmark: hard 17-clue 9x9 boards solved per second (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run does what `value` needs and no more: it generates the boards,
+warms up, times the K steps (every board of every step accounted for by the
+kernels' own counters), writes the last step's outputs if --dump-outputs is
+given and prints the line.  --full adds every other figure and check named
+below (`serial`, `single_batch`, `output_checks`, `p50_single_ms`,
+`cpu_baseline`, `side_configs`); on a plain run those fields are null.
 
 One process per GPU (torchrun for N > 1, RCCL for the barrier / max-time
 reduction only: boards are independent, each rank solves its own shard, no
@@ -14,7 +21,7 @@ ceil(K / 32) sdk_solve_batches launches -- one queue over up to 32 steps'
 batches that drains once, on a full grid, the next launch queued behind the
 running one -- each step keeping its own input (the batch rotated by 7919 j
 boards for step j) and output buffers.  value = all ranks' boards /
-max-over-ranks wall time.  Beside it, labelled: `serial` = the same K steps
+max-over-ranks wall time.  Beside it under --full, labelled: `serial` = the same K steps
 as K one-step launches back to back, `single_batch` = one step's batch in
 one solve() call (the "1M batch" alone), `output_checks` = every timed
 step's output checked (SOLVED, Sudoku.check, givens kept, equal across the
@@ -27,7 +34,10 @@ Rank 0 prints ONE JSON line with the contract fields plus:
                   timed GPU region per launch, HIP events; launch_ms = a
                   launch's own start-to-end span, overlapped with its
                   neighbours, which rocprofv3's kernel trace reports) and,
-                  as `hbm`, its algorithmic bytes per launch against HBM;
+                  as `hbm`, its algorithmic bytes per launch against HBM
+                  (read from committed files and the timed steps' own
+                  events: no run of its own);
+and with --full:
   cpu_baseline -- the oracle's literal reference walk (gen.py:6-28 restated in
                   C, oracle/) on a time-bounded sample of the same boards, one
                   walk per host core (affinity, capped by $OMP_NUM_THREADS),
@@ -120,6 +130,30 @@ def check_steps(solver, inputs, bufs, steps, group, lo, batch):
         sel = k_ref < shard
         ok["rotations_agree"] &= bool(torch.equal(out[sel], bufs[ref_b][0][k_ref[sel]]))
     return ok
+
+
+DUMP_BOARDS = 1 << 17  # boards of the last step written by --dump-outputs (float32: 43 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path: str, sols, status, suffix: str = "") -> dict:
+    """--dump-outputs: what the timed path handed back for its last step,
+    the (boards, 81) solutions and the (boards,) status words, as
+    <path>/solutions<suffix>.npy and <path>/status<suffix>.npy in float32.
+    More than DUMP_BOARDS boards: a fixed sample of them (DUMP_SEED, rising
+    positions; the same rows on every run of the same arguments)."""
+    import numpy as np
+    import torch
+    n = sols.shape[0]
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_BOARDS:
+        rows = np.sort(np.random.RandomState(DUMP_SEED).choice(n, DUMP_BOARDS, replace=False))
+        idx = torch.from_numpy(rows).to(sols.device)
+        sols, status = sols[idx], status[idx]
+    arrays = {"solutions": sols, "status": status}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a.cpu().numpy().astype(np.float32))
+    return {"dir": path, "boards": int(sols.shape[0]), "of": n, "files": [f"{k}{suffix}.npy" for k in arrays]}
 
 
 def _time(fn, reps=3):
@@ -430,6 +464,15 @@ def main():
     ap.add_argument("--launches", type=int, default=0,
                     help="split the timed steps' shards into this many launches of equal step counts "
                          "(sdk_solve_batches, <= SDK_MAX_BATCHES steps each) instead of --launch-boards")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the timed steps' outputs "
+                         "checked board for board, the serial and single-batch figures, single-board latency, the "
+                         "CPU baseline and the side configs (each with its own --no-... switch); off: the line's "
+                         "fields for them are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solutions and status words of the last timed step to "
+                         "DIR/solutions.npy and DIR/status.npy (float32; a fixed sample of 2^17 boards of a larger "
+                         "step; rank r > 0 of a multi-GPU run writes <name>_rank<r>.npy)")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--workload", choices=("hard17", "hard_search"), default="hard17",
                     help="timed boards: BASELINE's hard 17-clue set (default, the metric's config) or the "
@@ -474,6 +517,8 @@ def main():
                          "rank and takes the max).  Diagnostic: not the metric")
     ap.add_argument("--emulate-rank", type=int, default=0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps takes at least 1, --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -604,14 +649,20 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
-    checks = check_steps(solver, inputs, bufs, args.steps, group, lo, args.batch)
-    solved_ok = all(checks.values())
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step wrote pair (K - 1) % (m * group); nothing has touched it since
+        last = bufs[(args.steps - 1) % nb]
+        dumped = dump_outputs(args.dump_outputs, last[0], last[1], f"_rank{rank}" if rank else "")
+    # everything from here to the line is beside the headline figure: --full only
+    checks = check_steps(solver, inputs, bufs, args.steps, group, lo, args.batch) if args.full else None
+    solved_ok = all(checks.values()) if checks is not None else None
 
     # the same K steps as K one-step launches back to back (each its own
     # full grid and its own drain): what a run costs without plan "run"'s
     # one queue over the steps
     serial = None
-    if not args.no_serial:
+    if args.full and not args.no_serial:
         torch.cuda.synchronize(dev)
         s0 = time.perf_counter()
         solver.solve_inflight([inputs[i % group] for i in range(args.steps)], [bufs[i % nb][0] for i in range(args.steps)],
@@ -626,7 +677,7 @@ def main():
     # one step's batch alone: one device-resident solve() call (this rank's
     # shard of step 0, 2^20 boards at N = 1), best of 3
     single = None
-    if not args.no_serial:
+    if args.full and not args.no_serial:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         best = None
         for _ in range(3):
@@ -646,7 +697,7 @@ def main():
 
     # single-board latency (p50 over 32 boards, one launch each)
     lat = []
-    for i in range(args.latency_boards):
+    for i in range(args.latency_boards if args.full else 0):
         b = boards[i:i + 1]
         torch.cuda.synchronize(dev)
         s0 = time.perf_counter()
@@ -656,7 +707,7 @@ def main():
     lat.sort()
     p50 = lat[len(lat) // 2] if lat else None
 
-    extras = (None if args.no_extras or emulated
+    extras = (None if not args.full or args.no_extras or emulated
               else side_configs(solver, dev, world, rank, boards, serving=not args.no_serving))
 
     if rank != 0:
@@ -737,7 +788,7 @@ def main():
             roof["pass_ceiling_frac"] = st["sweeps"] / args.steps / kern_s / cp
 
     cpu = None
-    if world == 1 and not args.no_cpu and not emulated:
+    if args.full and world == 1 and not args.no_cpu and not emulated:
         sample = boards[:8192].cpu().numpy()
         done, el, threads = cpu_baseline(sample, args.cpu_budget)
         cpu = {"value": done / el, "unit": "boards/s", "cores": threads, "kind": "port",
@@ -782,6 +833,8 @@ def main():
         "roofline": roof,
         "cpu_baseline": cpu,
         "side_configs": extras,
+        "full": args.full,  # False: the fields only --full fills are null
+        "dumped_outputs": dumped,
     }
     print(json.dumps(line), flush=True)
     if world > 1:

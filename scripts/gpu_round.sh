@@ -25,8 +25,10 @@ timeout -k 10 900 python -u -m pytest tests -x -v --timeout 200 --timeout-method
 rc=$?; grep -E "passed|failed|FAILED|ERROR" gpurun_out/tall.log | tail -8; step pytest $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 rc=$?; tail -2 gpurun_out/smoke.log; step smoke $rc
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > gpurun_out/bench.json 2> gpurun_out/bench.err
-rc=$?; tail -c 600 gpurun_out/bench.json; step bench $rc
+# the full line (serial, single batch, p50, CPU baseline, side configs): $BENCH_OUT/bench.json
+BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench.json" 2> "$BENCH_OUT/bench.err"
+rc=$?; tail -c 600 "$BENCH_OUT/bench.json"; step bench $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_trace -o run --output-format csv -- python3 -u bench.py --steps 20 --warmup 5 --no-cpu --no-extras --no-serial --latency-boards 0 > gpurun_out/prof_trace.log 2>&1
 step trace $?
 python scripts/trace_summary.py gpurun_out/prof_trace/run_kernel_trace.csv gpurun_out/trace_summary.json --steps 20 > /dev/null

@@ -64,7 +64,7 @@ def test_bench_two_rank_path_runs():
         procs.append(subprocess.Popen(
             [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
              "--device-index", "0", "--steps", "2", "--warmup", "1", "--no-cpu", "--latency-boards", "4",
-             "--no-serving"],
+             "--no-serving", "--full"],
             cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -125,3 +125,69 @@ def test_check_steps_rotation_logic():
         bufs[2][0][0, k] = inputs[2][0, k]
         bufs[6][1][9] = 0
         assert not bench.check_steps(fs, inputs, bufs, 2 * group, group, lo, batch)["solved"]
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path):
+    """bench.dump_outputs on CPU tensors: a step of at most DUMP_BOARDS boards
+    is written whole, a larger one as the same DUMP_BOARDS rows (rising
+    positions) on every call; float32, solutions (n, 81) and status (n,)."""
+    import numpy as np
+    import torch
+    import bench
+
+    small = torch.randint(1, 10, (1000, 81), dtype=torch.uint8)
+    st = torch.ones(1000, dtype=torch.int32)
+    info = bench.dump_outputs(str(tmp_path / "a"), small, st)
+    got = np.load(tmp_path / "a" / "solutions.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy()) and info["boards"] == 1000
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), np.ones(1000, dtype=np.float32))
+
+    n = bench.DUMP_BOARDS + 12_345
+    big = (torch.arange(n, dtype=torch.int64)[:, None] * 7 + torch.arange(81)[None, :]).remainder(251).to(torch.uint8)
+    row = torch.arange(n, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "b"), big, row)
+    bench.dump_outputs(str(tmp_path / "c"), big.clone(), row.clone(), "_rank3")
+    rows = np.load(tmp_path / "b" / "status.npy")
+    assert rows.dtype == np.float32 and rows.shape == (bench.DUMP_BOARDS,) and (np.diff(rows) > 0).all()
+    sols = np.load(tmp_path / "b" / "solutions.npy")
+    assert sols.shape == (bench.DUMP_BOARDS, 81) and np.array_equal(sols, big.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "status_rank3.npy"))
+    assert np.array_equal(sols, np.load(tmp_path / "c" / "solutions_rank3.npy"))
+    assert sols.nbytes + rows.nbytes <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain bench.py run (no --full) in a fresh process: the line carries
+    the headline fields, the figures that take runs of their own are null,
+    and --dump-outputs holds the LAST timed step's answers: step 2 of 3 is
+    the batch rotated by 2 * 7919 boards, every board's one completion."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    from oracle import oracle as O
+    from sudoku_solver_distributed_amd.gen import hard17_batch
+    import bench
+
+    n, steps = 2048, 3
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", "1", "--batch", str(n), "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["unit"] == "boards/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    assert d["full"] is False
+    for k in ("serial", "single_batch", "output_checks", "p50_single_ms", "cpu_baseline", "side_configs"):
+        assert d[k] is None, k
+    sols = np.load(tmp_path / "out" / "solutions.npy")
+    st = np.load(tmp_path / "out" / "status.npy")
+    assert sols.dtype == np.float32 and sols.shape == (n, 81) and st.dtype == np.float32 and st.shape == (n,)
+    boards = hard17_batch(n, seed=2024).numpy()
+    last = boards[(np.arange(n) + bench.ROTATION * (steps - 1)) % n]
+    want, cnt = O.solve_unique_batch(last)
+    assert (cnt == 1).all() and (st == 1).all()
+    assert np.array_equal(sols, want.astype(np.float32))
