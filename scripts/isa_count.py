@@ -1,6 +1,6 @@
 """Static VALU count of one plane pass, for bench.py's useful_lane_frac:
-the loop body of scripts/microbench/pass_rate.hip (plane::pass alone on a
-register-resident board, same flags as the product build), minus its
+the loop body of scripts/microbench/pass_rate.hip (plane::pass_ahead, the
+lane loop's pass, alone on a register-resident board, same flags as the product build), minus its
 accumulate; and, for reference, the plane kernel's largest basic block
 (the pass inlined, with whatever the scheduler moved in or out of it).
 
@@ -48,7 +48,7 @@ def main():
     c, n = largest_block(MICRO, extra, "_Z9pass_loop")
     valu = sum(v for k, v in c.items() if k.startswith("v_")) - ACC_VALU
     ck, nk = largest_block(SRC, extra, "_Z12plane_kernel")
-    out = {"kernel": "plane_kernel", "source": "plane::pass alone (scripts/microbench/pass_rate.hip loop body, "
+    out = {"kernel": "plane_kernel", "source": "plane::pass_ahead alone (scripts/microbench/pass_rate.hip loop body, "
                                                "hipcc -O3 gfx950 %s)" % " ".join(extra),
            "pass_block_instructions": n, "valu_per_pass": valu,
            "salu_per_pass": sum(v for k, v in c.items() if k.startswith("s_")),

@@ -1,4 +1,4 @@
-// pass_rate.hip -- VALU issue ceiling of plane::pass at the plane kernel's
+// pass_rate.hip -- VALU issue ceiling of plane::pass_ahead (the lane loop's pass) at the plane kernel's
 // occupancy: every lane runs ITER passes on a board held in registers (no
 // queue, no I/O, no divergence).  Diagnostic, not product code.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-sched-strategy=iterative-ilp \
@@ -24,12 +24,12 @@ __global__ __launch_bounds__(256, WPE) void pass_loop(const uint32_t *boards, ui
     const uint32_t *src = boards + (size_t)(g % nboards) * 27;
 #pragma unroll
     for (int w = 0; w < 27; ++w) B.P[w / 3][w % 3] = src[w];
-    B.Det[0] = B.Det[1] = B.Det[2] = 0;
+    uint32_t und[3], nd[3];
+    plane::rule_a(B, nd);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) und[b] = plane::andn(plane::ROWS, nd[b]);
     uint32_t acc = 0;
-    for (int it = 0; it < ITER; ++it) {
-        uint32_t und[3];
-        acc += (uint32_t)plane::pass(B, und) + und[0] + und[1] + und[2];
-    }
+    for (int it = 0; it < ITER; ++it) acc += (uint32_t)plane::pass_ahead(B, und, nd) + und[0] + und[1] + und[2];
     sink[g] = acc;
 }
 

@@ -11,11 +11,20 @@ struct HostStack {
     uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_WORDS + k]; }
 };
 
-// trace[i * maxlen + k]: outcome of board i's pass k (0 OPEN, 1 DEAD = a
-// backtrack, 2 SOLVED, 3 STUCK = a guess); len[i] passes (capped at maxlen)
+// the lane loop's stack lines: the planes, the entry, and the level's
+// undetermined cells in words 28-30 (plane::pass_ahead's und)
+struct LineStack {
+    uint32_t w[82 * plane::STACK_LINE_WORDS];
+    void put(uint32_t d, int k, uint32_t v) { w[d * plane::STACK_LINE_WORDS + k] = v; }
+    uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_LINE_WORDS + k]; }
+};
+
+// trace[i * maxlen + k]: outcome of board i's pass k on the lane loop's
+// look-ahead pass (0 OPEN, 1 DEAD = a backtrack, 2 SOLVED, 3 STUCK = a
+// guess); len[i] passes (capped at maxlen)
 extern "C" void pass_trace(const uint8_t *in, int64_t n, int node_order, uint8_t *trace, int maxlen, uint32_t *len)
 {
-    static HostStack stk;
+    static LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
         uint8_t buf[84] = {0};
         memcpy(buf, in + i * 81, 81);
@@ -26,12 +35,20 @@ extern "C" void pass_trace(const uint8_t *in, int64_t n, int node_order, uint8_t
         plane::Board B;
         bool clash = false;
         len[i] = 0;
-        if (!plane::load_words(B, x, clash) || clash) continue;
+        uint32_t und[3], nd[3];
+        if (!plane::load_words(B, x, clash, nd) || clash) continue;
+        for (int b = 0; b < 3; ++b) und[b] = plane::ROWS & ~nd[b];
         uint32_t depth = 0, k = 0;
         uint8_t *t = trace + i * maxlen;
+        auto fix = [&](int band, int pos, uint32_t d) {
+            plane::set_cell(B, band, pos, d);
+            for (int b = 0; b < 3; ++b) {
+                nd[b] = b == band ? 1u << pos : 0u;
+                und[b] &= ~nd[b];
+            }
+        };
         for (;;) {
-            uint32_t und[3];
-            const int r = plane::pass(B, und);
+            const int r = plane::pass_ahead(B, und, nd);
             if (k < (uint32_t)maxlen) t[k] = (uint8_t)r;
             k++;
             if (r == plane::SOLVED) break;
@@ -43,8 +60,9 @@ extern "C" void pass_trace(const uint8_t *in, int64_t n, int node_order, uint8_t
                 const uint32_t d = cand & (0u - cand);
                 for (int w = 0; w < 27; ++w) stk.put(depth, w, B.P[w / 3][w % 3]);
                 stk.put(depth, plane::STACK_ENTRY, plane::make_entry(band, pos, cand ^ d));
+                for (int b = 0; b < 3; ++b) stk.put(depth, plane::STACK_UND + b, und[b]);
                 depth++;
-                plane::set_cell(B, band, pos, d);
+                fix(band, pos, d);
                 continue;
             }
             bool found = false;
@@ -55,10 +73,10 @@ extern "C" void pass_trace(const uint8_t *in, int64_t n, int node_order, uint8_t
                 if (!rem) continue;
                 const uint32_t d = rem & (0u - rem);
                 for (int w = 0; w < 27; ++w) B.P[w / 3][w % 3] = stk.get(depth, w);
-                B.Det[0] = B.Det[1] = B.Det[2] = 0;
+                for (int b = 0; b < 3; ++b) und[b] = stk.get(depth, plane::STACK_UND + b);
                 stk.put(depth, plane::STACK_ENTRY, e & ~(d << 8));
                 depth++;
-                plane::set_cell(B, (int)((e >> 5) & 3u), (int)(e & 31u), d);
+                fix((int)((e >> 5) & 3u), (int)(e & 31u), d);
                 found = true;
                 break;
             }

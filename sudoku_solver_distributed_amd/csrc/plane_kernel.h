@@ -8,9 +8,11 @@
 // over 64 lanes, LDS round trips and wave-uniform control.
 //
 // Execution: persistent lanes.  Each lane holds one board (27 plane words +
-// 3 bookkeeping words in VGPRs) and steps it one pass per loop iteration;
-// guesses push the 27 words + the branch entry to the lane's stack lines in
-// the workspace (PlaneStack).  Finished lanes wait until at least
+// 6 bookkeeping words in VGPRs: the undetermined cells and the determined
+// cells not yet removed from their peers) and steps it one look-ahead pass
+// (plane::pass_ahead) per loop iteration; guesses push the 27 words, the
+// branch entry and the undetermined cells to the lane's stack lines in the
+// workspace (PlaneStack).  Finished lanes wait until at least
 // SDK_PLANE_REFILL lanes of the wave are free, then stores and refills run
 // once for all of them: solved boards go to the wave's LDS outbox (written
 // out 64 at a time, a board per lane, as dwords), new boards come from the
@@ -93,8 +95,10 @@ typedef uint32_t sdk_v4u __attribute__((ext_vector_type(4)));
 
 // Per-lane DFS stack in the workspace: level L of lane g is one 128-byte
 // line at byte (g * PLANE_MAX_DEPTH + L) * 128, words 0..26 = the 27 planes
-// (word 3d+b = P[d][b]), word 27 = the branch entry, 28..31 unused.  A push
-// or pop is 7 buffer dwordx4 accesses to ONE line (guesses are lane-
+// (word 3d+b = P[d][b]), word 27 = the branch entry, words 28..30 = the
+// level's undetermined cells (plane::pass_ahead's und[]; the lanes' own: the
+// wave-wide solver and the pool records never read them), 31 unused.  A push
+// or pop is 8 buffer dwordx4 accesses to ONE line (guesses are lane-
 // divergent: a lane-interleaved layout made every push touch 28 lines).
 struct PlaneStack {
     __amdgpu_buffer_rsrc_t rsrc;
@@ -108,14 +112,16 @@ struct PlaneStack {
         asm("" : "+v"(x));
         return x;
     }
-    __device__ __forceinline__ void push(uint32_t level, plane::Board &B, uint32_t entry) const
+    __device__ __forceinline__ void push(uint32_t level, plane::Board &B, const uint32_t (&und)[3],
+                                         uint32_t entry) const
     {
         const int v = (int)voff(level);
         plane::pin_board(B);
 #define PQ(a, b, c, d) (sdk_v4u){B.P[a / 3][a % 3], B.P[b / 3][b % 3], B.P[c / 3][c % 3], B.P[d / 3][d % 3]}
         const sdk_v4u q0 = PQ(0, 1, 2, 3), q1 = PQ(4, 5, 6, 7), q2 = PQ(8, 9, 10, 11), q3 = PQ(12, 13, 14, 15),
                       q4 = PQ(16, 17, 18, 19), q5 = PQ(20, 21, 22, 23),
-                      q6 = (sdk_v4u){B.P[8][0], B.P[8][1], B.P[8][2], entry};
+                      q6 = (sdk_v4u){B.P[8][0], B.P[8][1], B.P[8][2], entry},
+                      q7 = (sdk_v4u){und[0], und[1], und[2], 0u};
 #undef PQ
         __builtin_amdgcn_raw_buffer_store_b128(q0, rsrc, v, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b128(q1, rsrc, v, 16, 0);
@@ -124,13 +130,14 @@ struct PlaneStack {
         __builtin_amdgcn_raw_buffer_store_b128(q4, rsrc, v, 64, 0);
         __builtin_amdgcn_raw_buffer_store_b128(q5, rsrc, v, 80, 0);
         __builtin_amdgcn_raw_buffer_store_b128(q6, rsrc, v, 96, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(q7, rsrc, v, 112, 0);
 #if SDK_PLANE_PUSH_PAD
         // a dwordx4 store reads its data registers after issue; hipcc pads a
         // following VALU write of them only when soffset is an inline constant,
         // and with a register soffset (offsets past 64) it has reused them at
-        // once.  Keeping all seven quads live through a 2-state pad makes
+        // once.  Keeping all eight quads live through a 2-state pad makes
         // every store read its data before any of them is overwritten.
-        asm volatile("s_nop 1" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(q5), "v"(q6));
+        asm volatile("s_nop 1" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(q5), "v"(q6), "v"(q7));
 #endif
     }
     // the last quad: planes 24..26 and the branch entry
@@ -140,8 +147,11 @@ struct PlaneStack {
     }
     // the whole line in one round trip: the entry (last quad) decides whether
     // the level still has a digit; if not (rare), the planes go unused
-    __device__ __forceinline__ uint32_t pop(uint32_t level, plane::Board &B) const { return pop_line(level, B)[3]; }
-    __device__ __forceinline__ sdk_v4u pop_line(uint32_t level, plane::Board &B) const
+    __device__ __forceinline__ uint32_t pop(uint32_t level, plane::Board &B, uint32_t (&und)[3]) const
+    {
+        return pop_line(level, B, und)[3];
+    }
+    __device__ __forceinline__ sdk_v4u pop_line(uint32_t level, plane::Board &B, uint32_t (&und)[3]) const
     {
         const int v = (int)voff(level);
         const sdk_v4u q0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 0, 0);
@@ -151,6 +161,8 @@ struct PlaneStack {
         const sdk_v4u q4 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 64, 0);
         const sdk_v4u q5 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 80, 0);
         const sdk_v4u t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 96, 0);
+        const sdk_v4u u = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 112, 0);
+        und[0] = u.x; und[1] = u.y; und[2] = u.z;
         B.P[0][0] = q0.x; B.P[0][1] = q0.y; B.P[0][2] = q0.z; B.P[1][0] = q0.w;
         B.P[1][1] = q1.x; B.P[1][2] = q1.y; B.P[2][0] = q1.z; B.P[2][1] = q1.w;
         B.P[2][2] = q2.x; B.P[3][0] = q2.y; B.P[3][1] = q2.z; B.P[3][2] = q2.w;
@@ -158,7 +170,7 @@ struct PlaneStack {
         B.P[5][1] = q4.x; B.P[5][2] = q4.y; B.P[6][0] = q4.z; B.P[6][1] = q4.w;
         B.P[6][2] = q5.x; B.P[7][0] = q5.y; B.P[7][1] = q5.z; B.P[7][2] = q5.w;
         B.P[8][0] = t.x; B.P[8][1] = t.y; B.P[8][2] = t.z;
-        // all seven loads issued before the caller's branch on the entry
+        // all eight loads issued before the caller's branch on the entry
         plane::pin_board(B);
         return t;
     }
@@ -851,6 +863,9 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
     uint32_t fin = 0, solved = 0, guesses = 0, passes = 0, deferred = 0;
     uint32_t bguess = 0;  // guesses on the current board (dropped if it is handed off)
     uint32_t mst = 0;     // the board's search mode and pass count (plane::search_step)
+    // the board's undetermined cells, and its determined cells not yet
+    // removed from their peers (plane::pass_ahead carries them from pass to pass)
+    uint32_t und[3] = {0u, 0u, 0u}, nd[3] = {0u, 0u, 0u};
     bool drained = false;  // the queue is empty and this wave's reservoir too
     // Board hand-out.  The first nt boards go out statically, 64 consecutive
     // ones per wave; the rest through the queue head (board nt + head).  A
@@ -899,13 +914,19 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
                 uint32_t x[21];
                 plane_stage_words(stage, sh + 81u * (uint32_t)r, x);
                 bool clash;  // tested lazily (see the unsolvable store above)
-                const bool ok = plane::load_words(B, x, clash);
+                uint32_t given[3];
+                const bool ok = plane::load_words(B, x, clash, given);
                 const bool cancel = ok && best && __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < q;
                 if (ok && !cancel) {
                     p = q;
                     depth = 0;
                     bguess = 0;
                     mst = 0;
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) {
+                        nd[b] = given[b];
+                        und[b] = plane::andn(plane::ROWS, given[b]);
+                    }
                     state = PL_ACTIVE;
                 } else {
                     const uint8_t *src = io.src(q);
@@ -1092,6 +1113,11 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
                         mst = 0;
                         if (!bad && !(best && __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p)) {
                             plane::planes_from_slices(B, V, given);
+#pragma unroll
+                            for (int b = 0; b < 3; ++b) {
+                                nd[b] = given[b];
+                                und[b] = plane::andn(plane::ROWS, given[b]);
+                            }
                             state = PL_ACTIVE;
                         } else {
                             state = PL_CANCELLED;  // (bad: SDK_INVALID below)
@@ -1145,8 +1171,7 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
         st_lanes += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
         st_piters++;
 #endif
-        uint32_t und[3];
-        const int r = plane::pass(B, und);
+        const int r = plane::pass_ahead(B, und, nd);
         if (r == plane::STUCK && best && __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p) {
             state = PL_CANCELLED;  // ordered mode: a lower board is solved
             continue;
@@ -1158,7 +1183,8 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
         const uint32_t st_d0 = depth;
         const uint64_t st_s0 = __builtin_amdgcn_s_memtime();
 #endif
-        const int s = plane::search_step(B, und, r, depth, mst, stk, node_order, PLANE_MAX_DEPTH, mrv_after, bguess);
+        const int s = plane::search_step_ahead(B, und, nd, r, depth, mst, stk, node_order, PLANE_MAX_DEPTH, mrv_after,
+                                               bguess);
 #if SDK_PLANE_STAMPS
         st_step += __builtin_amdgcn_s_memtime() - st_s0;
         st_push += wany(bguess != gb) ? 1u : 0u;

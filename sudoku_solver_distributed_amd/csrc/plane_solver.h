@@ -238,20 +238,12 @@ PS_FN uint32_t fold_rows(uint32_t y) { return (y | (y >> 10) | (y >> 20)) & 0x1F
 struct Board;
 PS_FN void pin_board(Board &B);
 
-// One propagation pass (rules A-D above).  Returns DEAD, SOLVED, STUCK (no
-// single found: und[] = the undetermined cells; rule D may still have
-// removed places, which the next pass sees) or OPEN (pass again).
-//
-// Written for the full-rate issue forms (see or3() above): two-input ops
-// with literal constants, three-input logic as v_bitop3_b32 on VGPRs, right
-// shifts only, 16-bit multiplies for 9-bit results, and one v_mul_u32_u24
-// per spread of a set over a band's three rows.  1797 VALU per pass with
-// SDK_PLANE_LC 3 (profiles/isa_plane_pass.json).
-PS_FN int pass(Board &B, uint32_t und[3])
+// Rule A on the board as it stands: single[] = the cells with exactly one
+// candidate; returns the cells with none (nonzero: the node is dead).
+PS_FN uint32_t rule_a(const Board &B, uint32_t (&single)[3])
 {
-    uint32_t single[3], nd[3];
-    uint32_t dead = 0;
-    // ---- A: determined cells.  o: >= 1 candidate, t: >= 2 candidates
+    uint32_t empty = 0;
+    // o: >= 1 candidate, t: >= 2 candidates
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
         // (every 3-input OR spelled as one bitop3: LLVM would fuse the
@@ -266,17 +258,24 @@ PS_FN int pass(Board &B, uint32_t und[3])
         o = or3(o, B.P[6][b], B.P[7][b]);
         t = or_and(t, o, B.P[8][b]);
         o |= B.P[8][b];
-        dead = or_andn(dead, ROWS, o);
+        empty = or_andn(empty, ROWS, o);
         single[b] = andn(o, t);
-        nd[b] = andn(single[b], B.Det[b]);
-        B.Det[b] = single[b];
-        und[b] = andn(ROWS, single[b]);
     }
-    const bool all_single = and3(single[0], single[1], single[2]) == ROWS;
-    const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
-    pin_board(B);
+    return empty;
+}
 
-    uint32_t hall[3] = {0u, 0u, 0u};
+// Rules B, C and D and the fix-up of one pass: nd[] = the determined cells
+// not yet removed from their peers.  hall[] = the hidden singles placed;
+// returns nonzero if a unit has lost a digit (the node is dead).
+//
+// Written for the full-rate issue forms (see or3() above): two-input ops
+// with literal constants, three-input logic as v_bitop3_b32 on VGPRs, right
+// shifts only, 16-bit multiplies for 9-bit results, and one v_mul_u32_u24
+// per spread of a set over a band's three rows.  With rule A, 1797 VALU per
+// pass with SDK_PLANE_LC 3 (profiles/isa_plane_pass.json).
+PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
+{
+    hall[0] = hall[1] = hall[2] = 0u;
 #if SDK_PLANE_GROUP > 1
     uint32_t hgrp[3] = {0u, 0u, 0u};
 #endif
@@ -445,7 +444,27 @@ PS_FN int pass(Board &B, uint32_t und[3])
             }
     }
 #endif
-    dead |= or3(rowall ^ GUARDS, colall ^ 0x1FFu, (boxall & BOXC) ^ BOXC);
+    return or3(rowall ^ GUARDS, colall ^ 0x1FFu, (boxall & BOXC) ^ BOXC);
+}
+
+// One propagation pass (rules A-D above), rule A first, on the state the
+// previous pass left.  Returns DEAD, SOLVED, STUCK (no single found: und[] =
+// the undetermined cells; rule D may still have removed places, which the
+// next pass sees) or OPEN (pass again).
+PS_FN int pass(Board &B, uint32_t und[3])
+{
+    uint32_t single[3], nd[3], hall[3];
+    uint32_t dead = rule_a(B, single);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        nd[b] = andn(single[b], B.Det[b]);
+        B.Det[b] = single[b];
+        und[b] = andn(ROWS, single[b]);
+    }
+    const bool all_single = and3(single[0], single[1], single[2]) == ROWS;
+    const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
+    pin_board(B);
+    dead |= pass_body(B, nd, hall);
     if (dead) return DEAD;
     if (all_single) return SOLVED;
     const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
@@ -453,6 +472,35 @@ PS_FN int pass(Board &B, uint32_t und[3])
     // branches one pass early, on sound planes -- host model: 21.389 against
     // 21.390 passes per board, DESIGN.md §4 -- and the step saves its
     // change tracking, 27 VALU)
+    return (any_nd || newh) ? OPEN : STUCK;
+}
+
+// The look-ahead pass: the same body, then rule A on the planes it leaves, so
+// the pass settles its own verdict instead of leaving it to the next one (a
+// branch this pass emptied is DEAD now; a pass after which nothing is pending
+// is STUCK now, not after one more pass that changes nothing).  Board::Det is
+// not used.  On entry und[] = the undetermined cells and nd[] = the
+// determined cells not yet removed from their peers; on return they describe
+// the new planes (what the next pass() would compute).  DEAD: a unit lost a
+// digit, or a cell is empty now; SOLVED: no cell was undetermined on entry
+// (this was the verifying pass); STUCK: no cell became determined and no
+// hidden single was placed; OPEN otherwise.
+PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3])
+{
+    uint32_t single[3], hall[3];
+    const bool all_single = or3(und[0], und[1], und[2]) == 0;
+    pin_board(B);
+    uint32_t dead = pass_body(B, nd, hall);
+    const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
+    dead |= rule_a(B, single);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        nd[b] = single[b] & und[b];
+        und[b] = andn(ROWS, single[b]);
+    }
+    if (dead) return DEAD;
+    if (all_single) return SOLVED;
+    const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
     return (any_nd || newh) ? OPEN : STUCK;
 }
 
@@ -694,14 +742,19 @@ PS_FN uint32_t slices_from_words(const uint32_t (&x)[21], uint32_t (&V)[4][3])
 
 // Load from 21 words x[k] = bytes 4k..4k+3 of the board (little endian; only
 // byte 80 of x[20] is used).  Returns false if a byte is > 9.
-PS_FN bool load_words(Board &B, const uint32_t (&x)[21], bool &clash)
+// given[]: the given cells (the determined cells of the loaded board).
+PS_FN bool load_words(Board &B, const uint32_t (&x)[21], bool &clash, uint32_t (&given)[3])
 {
     uint32_t V[4][3];
     const uint32_t badb = slices_from_words(x, V);
-    uint32_t given[3];
     planes_from_slices(B, V, given);
     clash = badb == 0 && givens_clash(B, given);
     return badb == 0;
+}
+PS_FN bool load_words(Board &B, const uint32_t (&x)[21], bool &clash)
+{
+    uint32_t given[3];
+    return load_words(B, x, clash, given);
 }
 
 // Store a SOLVED board: one byte per cell through `put(i, value)`.
@@ -727,8 +780,10 @@ PS_FN void store_values(const Board &B, Put put)
     }
 }
 
-// stack level: the 27 plane words + the branch entry
-enum { STACK_WORDS = 28, STACK_ENTRY = 27 };
+// stack level: the 27 plane words + the branch entry; on the look-ahead path
+// (pass_ahead) the level's undetermined cells follow in words 28-30 of a
+// 32-word line
+enum { STACK_WORDS = 28, STACK_ENTRY = 27, STACK_UND = 28, STACK_LINE_WORDS = 32 };
 // branch entry: bits 0-4 pos, 5-6 band, 8-16 untried digits
 PS_FN uint32_t make_entry(int band, int pos, uint32_t rem) { return (uint32_t)pos | ((uint32_t)band << 5) | (rem << 8); }
 
@@ -787,9 +842,17 @@ PS_FN bool root_counts(int mode, uint32_t depth, uint32_t mrv_after, uint32_t u0
 // (B holds the answer), S_NONE (no completion) or S_DEEP (deeper than the
 // stack: the board goes to the wave kernel).  mrv_after: passes before the
 // switch to the completion count (0 never).  guesses: +1 per branch node.
-template <class Stack>
-PS_FN int search_step(Board &B, const uint32_t (&und)[3], int r, uint32_t &depth, uint32_t &mst, const Stack &stk,
-                      int node_order, uint32_t max_depth, uint32_t mrv_after, uint32_t &guesses)
+//
+// AHEAD: the step after pass_ahead().  The board carries und[] / nd[] instead
+// of Det, and a stack level keeps its und[] with its planes: push(level, B,
+// und, entry), pop(level, B, und) -> entry.  A level is pushed when nothing
+// is pending (every determined cell removed from its peers), so a guess or a
+// backtrack leaves nd[] = the one cell it fixed, and a return to the root
+// nd[] = 0: no Det reset, and no repeat of rule B for all determined cells.
+template <bool AHEAD, class Stack>
+PS_FN int search_step_impl(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], int r, uint32_t &depth, uint32_t &mst,
+                           const Stack &stk, int node_order, uint32_t max_depth, uint32_t mrv_after,
+                           uint32_t &guesses)
 {
     mst++;
     int mode = mst_mode(mst);
@@ -855,10 +918,17 @@ PS_FN int search_step(Board &B, const uint32_t (&und)[3], int r, uint32_t &depth
             res = S_SOLVED;
         }
     }
-    if (save >= 0) stk.push((uint32_t)save, B, save_entry);
-    if (reload >= 0 || fresh) B.Det[0] = B.Det[1] = B.Det[2] = 0;
+    if constexpr (AHEAD) {
+        if (save >= 0) stk.push((uint32_t)save, B, und, save_entry);
+        if (reload >= 0) nd[0] = nd[1] = nd[2] = 0;
+    } else {
+        if (save >= 0) stk.push((uint32_t)save, B, save_entry);
+        if (reload >= 0 || fresh) B.Det[0] = B.Det[1] = B.Det[2] = 0;
+    }
     while (reload >= 0) {
-        const uint32_t e = stk.pop((uint32_t)reload, B);
+        uint32_t e;
+        if constexpr (AHEAD) e = stk.pop((uint32_t)reload, B, und);
+        else e = stk.pop((uint32_t)reload, B);
         if (!scan) break;
         const uint32_t rem = (e >> 8) & 0x1FFu;
         if (rem) {
@@ -892,8 +962,32 @@ PS_FN int search_step(Board &B, const uint32_t (&und)[3], int r, uint32_t &depth
         depth += last ? 0u : 1u;
         guesses++;
         set_cell(B, fix_band, fix_pos, fix_d);
+        if constexpr (AHEAD) {
+            const uint32_t cb = 1u << fix_pos;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                nd[b] = fix_band == b ? cb : 0u;
+                und[b] = andn(und[b], nd[b]);
+            }
+        }
     }
     return res;
+}
+
+template <class Stack>
+PS_FN int search_step(Board &B, const uint32_t (&und)[3], int r, uint32_t &depth, uint32_t &mst, const Stack &stk,
+                      int node_order, uint32_t max_depth, uint32_t mrv_after, uint32_t &guesses)
+{
+    uint32_t u[3] = {und[0], und[1], und[2]}, n[3] = {0u, 0u, 0u};
+    return search_step_impl<false>(B, u, n, r, depth, mst, stk, node_order, max_depth, mrv_after, guesses);
+}
+
+template <class Stack>
+PS_FN int search_step_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], int r, uint32_t &depth, uint32_t &mst,
+                            const Stack &stk, int node_order, uint32_t max_depth, uint32_t mrv_after,
+                            uint32_t &guesses)
+{
+    return search_step_impl<true>(B, und, nd, r, depth, mst, stk, node_order, max_depth, mrv_after, guesses);
 }
 
 // the step's stack interface over a word stack with put(level, k, v) / get(level, k)
@@ -909,6 +1003,18 @@ struct WordStack {
     {
         load(level, B);
         return s.get(level, STACK_ENTRY);
+    }
+    // the look-ahead path's level: the planes, the entry and und[] (the
+    // stack's lines hold STACK_LINE_WORDS words)
+    PS_MF void push(uint32_t level, const Board &B, const uint32_t (&und)[3], uint32_t entry) const
+    {
+        push(level, B, entry);
+        for (int b = 0; b < 3; ++b) s.put(level, STACK_UND + b, und[b]);
+    }
+    PS_MF uint32_t pop(uint32_t level, Board &B, uint32_t (&und)[3]) const
+    {
+        for (int b = 0; b < 3; ++b) und[b] = s.get(level, STACK_UND + b);
+        return pop(level, B);
     }
     PS_MF void put_entry(uint32_t level, uint32_t e) const { s.put(level, STACK_ENTRY, e); }
     PS_MF void load(uint32_t level, Board &B) const
@@ -938,6 +1044,26 @@ PS_FN int solve(Board &B, Stack &stk, int node_order, uint32_t max_depth, Stats 
         const int r = pass(B, und);
         st.passes++;
         const int s = search_step(B, und, r, depth, mst, ws, node_order, max_depth, mrv_after, st.guesses);
+        if (s == S_CONT) continue;
+        return s == S_SOLVED ? 1 : s == S_NONE ? 0 : -1;
+    }
+}
+
+// The same driver on the look-ahead pass (the plane kernel's lane loop):
+// und[] / nd[] start from rule A on the board as loaded (a fresh board's
+// determined cells are its givens).  The stack's lines hold STACK_LINE_WORDS
+// words.
+template <typename Stack>
+PS_FN int solve_ahead(Board &B, Stack &stk, int node_order, uint32_t max_depth, Stats &st, uint32_t mrv_after = 0)
+{
+    const WordStack<Stack> ws = {stk};
+    uint32_t depth = 0, mst = 0, und[3], nd[3];
+    if (rule_a(B, nd)) return 0;  // a cell with no candidate
+    for (int b = 0; b < 3; ++b) und[b] = andn(ROWS, nd[b]);
+    for (;;) {
+        const int r = pass_ahead(B, und, nd);
+        st.passes++;
+        const int s = search_step_ahead(B, und, nd, r, depth, mst, ws, node_order, max_depth, mrv_after, st.guesses);
         if (s == S_CONT) continue;
         return s == S_SOLVED ? 1 : s == S_NONE ? 0 : -1;
     }
