@@ -227,6 +227,40 @@ int sdk_set_plane_tuning(int refill, int tail, int tail_mode, int chunk);
  * (nothing changed). */
 int sdk_set_plane_search(int mrv_after);
 
+/* Count the completions of n boards, capped (library extension, no reference
+ * counterpart: the reference only ever asks for one completion):
+ *   d_count[i] = min(limit, number of completions of board i that are valid
+ *                Sudoku grids -- every row, column and box holds 1..9 once,
+ *                the givens kept),   1 <= limit <= SDK_COUNT_MAX_LIMIT.
+ * A board whose givens repeat a digit in a row, column or box has count 0.
+ * This deliberately DIFFERS from sdk_solve_batch: the reference walk never
+ * tests the givens and may "solve" such a board; the count is about valid
+ * grids only.  A byte > 9 gives SDK_INVALID in d_count[i]; SDK_FAULT would
+ * mean the search outgrew its stack, which 81 levels make impossible.
+ * d_first (may be NULL, must not alias d_puzzles): per board 81 bytes -- for
+ * count >= 1 a completion, the first one the count's search met (for
+ * count == 1 necessarily the walk's answer); for count <= 0 the input board.
+ * d_scratch: at least sdk_count_scratch_bytes(n, max_waves) bytes of device
+ * memory, contents irrelevant: the call re-arms its queue head itself on
+ * `stream`.  A scratch is SINGLE-STREAM like a workspace; the solve
+ * workspace, its counters and sdk_verify_workspace are not involved.
+ * max_waves caps the kernel's grid (0: as many waves as fit on the device at
+ * the kernel's occupancy); results never depend on it.  The scratch holds the
+ * per-lane search stacks of min(ceil(n / 64), waves) waves, about 660 KB per
+ * wave: little for a small call, about 2.7 GB for a full grid on an MI355X.
+ * The limit bounds the work per completion found, not the work to prove
+ * that a sparse board has none.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * limit out of range, negative n or max_waves, a NULL pointer that is
+ * required, scratch too small), by return code only (sdk_last_error() is not
+ * set); arguments are checked before any launch and n == 0 returns 0.
+ * sdk_count_scratch_bytes returns 0 for negative arguments. */
+#define SDK_COUNT_MAX_LIMIT 1024
+size_t sdk_count_scratch_bytes(int64_t n, int max_waves);
+int sdk_count_solutions_batch(const uint8_t *d_puzzles, int32_t *d_count, uint8_t *d_first /* NULL ok */,
+                              int64_t n, int limit, void *d_scratch, size_t scratch_bytes,
+                              int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

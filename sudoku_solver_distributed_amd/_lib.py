@@ -17,6 +17,7 @@ SDK_UNSOLVABLE = 0
 SDK_SOLVED = 1
 SDK_INVALID = -1
 SDK_CANCELLED = -2
+SDK_FAULT = -3       # internal consistency check failed (never expected)
 SDK_NO_RETURN = -4   # sdk_peer_solve_batch: node.py's /solve loop never returns
 SDK_PEER_STATE_BYTES = 1600  # sdk_peer_solve_seq: one node's partial_solution + tried sets
 SDK_ORDER_GEN = 0    # gen.py:6-28's walk (last row with an empty cell first)
@@ -43,9 +44,12 @@ EXPORTS = (
     "sdk_set_solve_kernel",
     "sdk_set_plane_tuning",
     "sdk_set_plane_search",
+    "sdk_count_scratch_bytes",
+    "sdk_count_solutions_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
+SDK_COUNT_MAX_LIMIT = 1024  # sdk_count_solutions_batch: the largest cap
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -105,6 +109,10 @@ def load() -> ctypes.CDLL:
     L.sdk_set_plane_tuning.argtypes = [i32, i32, i32, i32]
     L.sdk_set_plane_search.restype = i32
     L.sdk_set_plane_search.argtypes = [i32]
+    L.sdk_count_scratch_bytes.restype = sz
+    L.sdk_count_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_count_solutions_batch.restype = i32
+    L.sdk_count_solutions_batch.argtypes = [vp, vp, vp, i64, i32, vp, sz, i32, vp]
     _lib = L
     return L
 

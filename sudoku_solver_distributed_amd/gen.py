@@ -15,6 +15,10 @@
   data/hard17_classes.txt (scripts/make_hard17.py).
 * ``hard_search_batch(n, seed)`` -- the search-heavy set: the same symmetries
   applied to 256 minimal puzzles that need real search (data/).
+* ``unique_batch(n, empty_boxes, seed)`` -- proper puzzles: boards with exactly
+  one solution (minimal ones by default), certified removal by removal by the
+  GPU's completion count (library extension; the reference's generate_sudoku
+  erases cells blindly and its 55-empty boards are almost never unique).
 """
 from __future__ import annotations
 
@@ -128,6 +132,40 @@ def generate_batch(n: int, empty_boxes: int, seed: Optional[int] = None, device=
                               device=puzzles.device)
         puzzles.scatter_(1, idx, 0)
     return (puzzles, full) if return_solutions else puzzles
+
+
+def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, device=None,
+                 return_solutions: bool = False):
+    """n puzzles with exactly ONE solution, as a (n, 81) uint8 device tensor
+    (and their full grids).  Library extension, no reference counterpart.
+
+    1. full = generate_batch(n, 0, seed): the full grids.
+    2. order = argsort(default_rng(seed).random((n, 81)), axis=1): each
+       board's own random order of its 81 cells.
+    3. puzzle = full; for round t = 0..80, every board that still has fewer
+       than `empty_boxes` empties tries its puzzle with cell order[i, t]
+       erased; ONE count_solutions(trials, limit=2) call certifies the whole
+       batch, and a removal is kept where the count is 1.
+
+    Every board has one completion (its full grid) and at most `empty_boxes`
+    empties.  With empty_boxes=81 every puzzle is minimal: each cell was tried
+    once, and a removal that loses uniqueness loses it under any further
+    removals too."""
+    solver = get_solver(device)
+    full = generate_batch(n, 0, seed, device=device)
+    order = np.argsort(np.random.default_rng(seed).random((n, 81)), axis=1)
+    order = torch.as_tensor(order, dtype=torch.int64, device=full.device)
+    puzzle = full.clone()
+    empties = torch.zeros(n, dtype=torch.int64, device=full.device)
+    zero = torch.zeros((), dtype=torch.uint8, device=full.device)
+    for t in range(81 if n and empty_boxes > 0 else 0):
+        cell = order[:, t:t + 1]
+        live = (empties < empty_boxes).unsqueeze(1)
+        trial = puzzle.scatter(1, cell, torch.where(live, zero, puzzle.gather(1, cell)))
+        keep = live & (solver.count_solutions(trial, limit=2) == 1).unsqueeze(1)
+        puzzle = torch.where(keep, trial, puzzle)
+        empties += keep.squeeze(1)
+    return (puzzle, full) if return_solutions else puzzle
 
 
 # ------------------------------------------------------------ hard 17-clue set

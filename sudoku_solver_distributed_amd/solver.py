@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import SDK_CANCELLED, SDK_INVALID, SDK_NO_RETURN, SDK_SOLVED, SDK_UNSOLVABLE, SudokuHipError
+from ._lib import (SDK_CANCELLED, SDK_COUNT_MAX_LIMIT, SDK_INVALID, SDK_NO_RETURN, SDK_SOLVED, SDK_UNSOLVABLE,
+                   SudokuHipError)
 
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
@@ -128,6 +129,7 @@ class BatchSolver:
         self._pool = None  # the solver's streams (_stream_pool)
         self._slots = None  # solve_inflight's (solver, stream) slots (_slot_solvers)
         self._pool_lock = threading.Lock()  # builds _pool / _slots once across threads
+        self._count_scratch = None  # count_solutions' scratch, grown on demand (under self._lock)
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -181,6 +183,42 @@ class BatchSolver:
                                                _grid_arg(grid_waves, pipelined))
         _lib.check(rc, "sdk_solve_batch_grid")
         return out, status
+
+    # -------------------------------------------------------------- count
+    def count_solutions(self, puzzles, limit: int = 2, return_first: bool = False, stream=None, max_waves: int = 0):
+        """counts[i] = min(limit, completions of board i that are valid Sudoku
+        grids) as an int32 (n,) tensor (sdk_count_solutions_batch; library
+        extension, no reference counterpart).  1 <= limit <= 1024.  A board
+        whose givens repeat a digit in a unit counts 0 -- unlike solve(), whose
+        walk never tests the givens; a byte > 9 gives SDK_INVALID (-1).
+        return_first: also an (n, 81) tensor with a completion of every board
+        that has one (the unique one when the count at limit >= 2 is 1) and
+        the input board otherwise.  max_waves > 0 caps the kernel's grid;
+        results never depend on it.  Asynchronous on the stream; one cached
+        scratch tensor serves every call, ordered like the workspace's."""
+        limit = int(limit)
+        if not 1 <= limit <= SDK_COUNT_MAX_LIMIT:
+            raise ValueError(f"limit must be 1..{SDK_COUNT_MAX_LIMIT}")
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = self._dev(as_boards(puzzles, max_value=255))
+        n = p.shape[0]
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        first = torch.empty_like(p) if return_first else None
+        with self._lock, torch.cuda.device(self.device):
+            need = int(self.lib.sdk_count_scratch_bytes(n, int(max_waves)))
+            sc = self._count_scratch
+            if sc is None or sc.numel() < need:
+                if sc is not None and self._last_stream is not None:
+                    sc.record_stream(self._last_stream)  # a count may still be running on it
+                sc = self._count_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            rc = self.lib.sdk_count_solutions_batch(p.data_ptr(), counts.data_ptr(),
+                                                    first.data_ptr() if return_first else None, n, limit,
+                                                    sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
+        if rc != 0:  # (reported by return code only: the entry does not set sdk_last_error)
+            raise SudokuHipError(f"sdk_count_solutions_batch failed ({rc}): "
+                                 + ("HIP error" if rc == -1 else "bad arguments"))
+        return (counts, first) if return_first else counts
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
