@@ -261,6 +261,43 @@ int sdk_count_solutions_batch(const uint8_t *d_puzzles, int32_t *d_count, uint8_
                               int64_t n, int limit, void *d_scratch, size_t scratch_bytes,
                               int max_waves, void *stream);
 
+/* Canonical form of n boards under Sudoku's symmetries (library extension, no
+ * reference counterpart).  A board is 81 bytes 0..9; whether it obeys the
+ * rules plays no part.  A line permutation p in [0, 1296) is
+ * p = ((bp*6 + a)*6 + b)*6 + d with PERM3 = {012, 021, 102, 120, 201, 210}:
+ *   perm_p[k] = 3*PERM3[bp][k/3] + PERM3[(a, b, d)[k/3]][k%3].
+ * Symmetry sym = (t*1296 + ri)*1296 + ci, t in {0, 1}, R = perm_ri,
+ * C = perm_ci: image cell (i, j) = g[R[i]][C[j]] for t == 0, g[C[j]][R[i]]
+ * for t == 1; the image's non-zero digits are then relabelled 1, 2, ... in
+ * order of first appearance in row-major order, zeros stay zero.
+ *   d_canon[i] = the lexicographically smallest image of board i over all
+ *                SDK_CANON_SYMMETRIES sym (bytes compared 0 < 1 < ... < 9),
+ *   d_sym[i]   = the smallest sym whose image it is,
+ *   d_autos[i] = the number of sym whose image it is (for a valid grid the
+ *                order of its automorphism group within this group).
+ * Two boards are the same puzzle under these symmetries exactly when their
+ * canonical forms are equal.  A board with a byte > 9 comes back as it is,
+ * with SDK_INVALID in d_sym[i] and d_autos[i].  d_autos may be NULL; d_canon
+ * must not alias d_boards.
+ * slices: every board's search is cut into that many parts, one workgroup
+ * each (1..SDK_CANON_MAX_SLICES); 0 picks enough of them for a small batch
+ * to fill the device (1 for a large batch).  Results never depend on it.
+ * d_scratch: at least sdk_canonical_scratch_bytes(n, slices) bytes of device
+ * memory (64 bytes per board and slice), contents irrelevant; SINGLE-STREAM
+ * like a workspace.  The solve workspace is not involved.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * slices out of range, negative n, a NULL pointer that is required, d_canon
+ * == d_boards, scratch too small), by return code only; arguments are
+ * checked before any launch and n == 0 returns 0.
+ * sdk_canonical_scratch_bytes returns 0 for negative or out-of-range
+ * arguments. */
+#define SDK_CANON_SYMMETRIES 3359232
+#define SDK_CANON_MAX_SLICES 2592
+size_t sdk_canonical_scratch_bytes(int64_t n, int slices);
+int sdk_canonical_batch(const uint8_t *d_boards, uint8_t *d_canon, int32_t *d_sym, int32_t *d_autos /* NULL ok */,
+                        int64_t n, int slices /* 0 = auto */, void *d_scratch, size_t scratch_bytes,
+                        void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -46,10 +46,14 @@ EXPORTS = (
     "sdk_set_plane_search",
     "sdk_count_scratch_bytes",
     "sdk_count_solutions_batch",
+    "sdk_canonical_scratch_bytes",
+    "sdk_canonical_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
 SDK_COUNT_MAX_LIMIT = 1024  # sdk_count_solutions_batch: the largest cap
+SDK_CANON_SYMMETRIES = 3359232  # sdk_canonical_batch: 2 * 1296 * 1296
+SDK_CANON_MAX_SLICES = 2592  # ... and the most parts a board's search is cut into
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -113,6 +117,10 @@ def load() -> ctypes.CDLL:
     L.sdk_count_scratch_bytes.argtypes = [i64, i32]
     L.sdk_count_solutions_batch.restype = i32
     L.sdk_count_solutions_batch.argtypes = [vp, vp, vp, i64, i32, vp, sz, i32, vp]
+    L.sdk_canonical_scratch_bytes.restype = sz
+    L.sdk_canonical_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_canonical_batch.restype = i32
+    L.sdk_canonical_batch.argtypes = [vp, vp, vp, vp, i64, i32, vp, sz, vp]
     _lib = L
     return L
 

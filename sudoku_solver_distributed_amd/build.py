@@ -14,7 +14,8 @@ ROOT = os.path.dirname(_HERE)
 # count_kernels.hip, the completion count, is a unit of its own so that the
 # solve kernels' code generation and scheduler flags stay exactly as they are;
 # iterative-minreg keeps its board loader from spilling: 116 VGPRs and no
-# scratch, where LLVM's default scheduler spills 34 registers)
+# scratch, where LLVM's default scheduler spills 34 registers, DESIGN.md §12;
+# canon_kernels.hip, the canonical form, likewise its own unit, LLVM's defaults)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -31,7 +32,8 @@ def sources(sched: str = _SCHED):
     extra = [f for o in _LLVM_EXTRA for f in ("-mllvm", o)]
     return (("sudoku_kernels.hip", []),
             ("plane_kernels.hip", ([] if sched == "default" else ["-mllvm", f"-amdgpu-sched-strategy={sched}"]) + extra),
-            ("count_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
+            ("count_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
+            ("canon_kernels.hip", []))
 
 
 SRCS = sources()

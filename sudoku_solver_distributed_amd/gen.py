@@ -19,6 +19,9 @@
   one solution (minimal ones by default), certified removal by removal by the
   GPU's completion count (library extension; the reference's generate_sudoku
   erases cells blindly and its 55-empty boards are almost never unique).
+* ``apply_symmetry(boards, sym)`` / ``class_ids(boards)`` -- the symmetry
+  group in numbers and the isomorphism class of every board, by the GPU's
+  canonical form (BatchSolver.canonical; library extension).
 """
 from __future__ import annotations
 
@@ -135,7 +138,7 @@ def generate_batch(n: int, empty_boxes: int, seed: Optional[int] = None, device=
 
 
 def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, device=None,
-                 return_solutions: bool = False):
+                 return_solutions: bool = False, distinct: bool = False):
     """n puzzles with exactly ONE solution, as a (n, 81) uint8 device tensor
     (and their full grids).  Library extension, no reference counterpart.
 
@@ -150,7 +153,12 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
     Every board has one completion (its full grid) and at most `empty_boxes`
     empties.  With empty_boxes=81 every puzzle is minimal: each cell was tried
     once, and a removal that loses uniqueness loses it under any further
-    removals too."""
+    removals too.
+
+    distinct=True keeps only the first puzzle of every isomorphism class
+    (class_ids), in the batch's order, and the matching rows of the full
+    grids: fewer than n boards when two puzzles are symmetry images of each
+    other."""
     solver = get_solver(device)
     full = generate_batch(n, 0, seed, device=device)
     order = np.argsort(np.random.default_rng(seed).random((n, 81)), axis=1)
@@ -165,7 +173,73 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
         keep = live & (solver.count_solutions(trial, limit=2) == 1).unsqueeze(1)
         puzzle = torch.where(keep, trial, puzzle)
         empties += keep.squeeze(1)
+    if distinct and n:
+        first = torch.sort(class_ids(puzzle, device=device)[2]).values
+        puzzle, full = puzzle[first], full[first]
     return (puzzle, full) if return_solutions else puzzle
+
+
+# ------------------------------------------------------------ symmetry classes
+_PERM3 = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+CANON_SYMMETRIES = 2 * 1296 * 1296
+
+
+def line_perms() -> np.ndarray:
+    """The 1296 line permutations as a (1296, 9) array: number
+    p = ((bp*6 + a)*6 + b)*6 + d is perm[k] = 3*PERM3[bp][k//3] +
+    PERM3[(a, b, d)[k//3]][k%3] (include/sudoku_hip.h, sdk_canonical_batch)."""
+    out = np.empty((1296, 9), dtype=np.int64)
+    for p in range(1296):
+        bp, inner = p // 216, ((p // 36) % 6, (p // 6) % 6, p % 6)
+        out[p] = [3 * _PERM3[bp][k // 3] + _PERM3[inner[k // 3]][k % 3] for k in range(9)]
+    return out
+
+
+def apply_symmetry(boards, sym):
+    """The image of every board under its symmetry number, straight from the
+    definition (pure numpy, independent of the kernel): sym = (t*1296 + ri)*1296
+    + ci; image cell (i, j) = g[R[i]][C[j]], or g[C[j]][R[i]] when t == 1; then
+    the non-zero digits relabelled 1, 2, ... in order of first appearance.
+    boards: (n, 81) with bytes 0..9; sym: n numbers in [0, 3359232) (or one
+    for all).  Returns (images (n, 81) uint8, digit_maps (n, 10) uint8) with
+    digit_maps[i, x] = the label digit x of board i got (0: x is 0 or absent)
+    -- tensors on the boards' device if `boards` is a tensor, else arrays."""
+    as_tensor = isinstance(boards, torch.Tensor)
+    b = (boards.cpu().numpy() if as_tensor else np.asarray(boards)).astype(np.uint8).reshape(-1, 81)
+    s = sym.cpu().numpy() if isinstance(sym, torch.Tensor) else np.asarray(sym)
+    s = np.broadcast_to(s.astype(np.int64).reshape(-1), (len(b),))
+    if b.size and b.max() > 9:
+        raise ValueError("board cells must be 0..9")
+    if len(s) and (s.min() < 0 or s.max() >= CANON_SYMMETRIES):
+        raise ValueError(f"sym must be in [0, {CANON_SYMMETRIES})")
+    perms = line_perms()
+    t, R, C = s // (1296 * 1296), perms[(s // 1296) % 1296], perms[s % 1296]
+    r, c = R[:, :, None], C[:, None, :]
+    src = np.where(t[:, None, None] == 1, c * 9 + r, r * 9 + c).reshape(-1, 81)
+    img = np.take_along_axis(b, src, axis=1)
+    # the first position of every digit (81: absent) ranks the digits
+    first = np.stack([np.where((img == x).any(1), (img == x).argmax(1), 81) for x in range(1, 10)], axis=1)
+    label = 1 + (first[:, None, :] < first[:, :, None]).sum(2)
+    maps = np.zeros((len(b), 10), dtype=np.uint8)
+    maps[:, 1:] = np.where(first < 81, label, 0)
+    out = np.take_along_axis(maps, img.astype(np.int64), axis=1)
+    if as_tensor:
+        return torch.from_numpy(out).to(boards.device), torch.from_numpy(maps).to(boards.device)
+    return out, maps
+
+
+def class_ids(boards, device=None):
+    """The isomorphism class of every board: (canon, ids, first_index) --
+    canon (n, 81) uint8, the canonical forms (BatchSolver.canonical); ids
+    (n,) int64, a dense class number per board (classes numbered in the
+    lexicographic order of their canonical forms); first_index (classes,)
+    int64, the index of each class's first member.  Device tensors."""
+    canon = get_solver(device).canonical(boards)
+    n = canon.shape[0]
+    uniq, ids = torch.unique(canon, dim=0, return_inverse=True)
+    first = torch.full((uniq.shape[0],), n, dtype=torch.int64, device=canon.device)
+    first.scatter_reduce_(0, ids, torch.arange(n, dtype=torch.int64, device=canon.device), reduce="amin")
+    return canon, ids, first
 
 
 # ------------------------------------------------------------ hard 17-clue set

@@ -130,6 +130,7 @@ class BatchSolver:
         self._slots = None  # solve_inflight's (solver, stream) slots (_slot_solvers)
         self._pool_lock = threading.Lock()  # builds _pool / _slots once across threads
         self._count_scratch = None  # count_solutions' scratch, grown on demand (under self._lock)
+        self._canon_scratch = None  # canonical's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -219,6 +220,47 @@ class BatchSolver:
             raise SudokuHipError(f"sdk_count_solutions_batch failed ({rc}): "
                                  + ("HIP error" if rc == -1 else "bad arguments"))
         return (counts, first) if return_first else counts
+
+    # ---------------------------------------------------------- canonical
+    def canonical(self, boards, return_sym: bool = False, return_autos: bool = False, slices: int = 0, stream=None):
+        """The canonical (minlex) form of every board under Sudoku's
+        symmetries -- transposition, band / stack permutations, row / column
+        permutations inside them, digit relabelling -- as an (n, 81) uint8
+        tensor (sdk_canonical_batch; library extension, no reference
+        counterpart; the definition is in include/sudoku_hip.h).  Two boards
+        are the same puzzle under the symmetries exactly when their canonical
+        forms are equal.  Any bytes 0..9 count as a board, valid or not.
+        return_sym: also an int32 (n,) tensor, the smallest symmetry number
+        whose image the form is (gen.apply_symmetry applies it);
+        return_autos: also int32 (n,), how many of the 3 359 232 symmetries
+        give it.  A board with a byte > 9 comes back as it is with
+        SDK_INVALID (-1) in both.  slices cuts each board's search into that
+        many workgroups (0: enough for a small batch to fill the device);
+        results never depend on it.  Asynchronous on the stream; one cached
+        scratch tensor serves every call, ordered like the workspace's."""
+        slices = int(slices)
+        if not 0 <= slices <= _lib.SDK_CANON_MAX_SLICES:
+            raise ValueError(f"slices must be 0 (auto) or 1..{_lib.SDK_CANON_MAX_SLICES}")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        canon = torch.empty_like(p)
+        sym = torch.empty(n, dtype=torch.int32, device=self.device)
+        autos = torch.empty(n, dtype=torch.int32, device=self.device) if return_autos else None
+        with self._lock, torch.cuda.device(self.device):
+            need = int(self.lib.sdk_canonical_scratch_bytes(n, slices))
+            sc = self._canon_scratch
+            if sc is None or sc.numel() < need:
+                if sc is not None and self._last_stream is not None:
+                    sc.record_stream(self._last_stream)  # a call may still be running on it
+                sc = self._canon_scratch = torch.empty(max(need, 64), dtype=torch.uint8, device=self.device)
+            rc = self.lib.sdk_canonical_batch(p.data_ptr(), canon.data_ptr(), sym.data_ptr(),
+                                              autos.data_ptr() if return_autos else None, n, slices,
+                                              sc.data_ptr(), sc.numel(), self._ws_stream(stream))
+        if rc != 0:  # (reported by return code only: the entry does not set sdk_last_error)
+            raise SudokuHipError(f"sdk_canonical_batch failed ({rc}): "
+                                 + ("HIP error" if rc == -1 else "bad arguments"))
+        out = (canon,) + ((sym,) if return_sym else ()) + ((autos,) if return_autos else ())
+        return out if len(out) > 1 else canon
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
