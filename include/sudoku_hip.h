@@ -105,7 +105,7 @@ int sdk_check_batch(const uint8_t *d_grids, int32_t *d_ok, int64_t n, int mode, 
 /* Batch of node.py "solve" tasks (node.py:384-406 -> 76-80,
  * SudokuSolver.solve_sudoku_destributed): d_num[i] = first digit 1..9 that
  * is_valid_move (node.py:42-60) accepts at cell d_cells[i] (= row*9+col) of
- * board i, or 0 for None. */
+ * board i, or 0 for None.  A cell index outside 0..80 gives d_num[i] = -1. */
 int sdk_first_candidate_batch(const uint8_t *d_grids, const int32_t *d_cells,
                               int32_t *d_num, int64_t n, void *stream);
 
@@ -145,6 +145,7 @@ int sdk_peer_solve_seq(const uint8_t *d_boards, uint8_t *d_out, int32_t *d_statu
  *   solved -> one child: the solved grid,
  *   open   -> one child per candidate of the walk's next cell (`order`),
  *             digits ascending.
+ * A node with a byte > 9 gets no child either (it is not propagated).
  * Children of all nodes, concatenated in input order, are therefore in the
  * walk's (lexicographic) order, and the first SOLVED child of the frontier
  * carries the walk's first solution.
