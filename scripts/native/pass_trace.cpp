@@ -1,37 +1,17 @@
 // pass_trace.cpp -- per-board pass outcome sequences of the lane solver
 // (plane_solver.h on the host), for scripts/wave_events.py: how often a wave
 // of 64 lanes runs the push / pop paths, refills and stores.  Tooling only.
-#include <stdint.h>
-#include <string.h>
-#include "../../sudoku_solver_distributed_amd/csrc/plane_solver.h"
-
-struct HostStack {
-    uint32_t w[82 * plane::STACK_WORDS];
-    void put(uint32_t d, int k, uint32_t v) { w[d * plane::STACK_WORDS + k] = v; }
-    uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_WORDS + k]; }
-};
-
-// the lane loop's stack lines: the planes, the entry, and the level's
-// undetermined cells in words 28-30 (plane::pass_ahead's und)
-struct LineStack {
-    uint32_t w[82 * plane::STACK_LINE_WORDS];
-    void put(uint32_t d, int k, uint32_t v) { w[d * plane::STACK_LINE_WORDS + k] = v; }
-    uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_LINE_WORDS + k]; }
-};
+#include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
 
 // trace[i * maxlen + k]: outcome of board i's pass k on the lane loop's
 // look-ahead pass (0 OPEN, 1 DEAD = a backtrack, 2 SOLVED, 3 STUCK = a
 // guess); len[i] passes (capped at maxlen)
 extern "C" void pass_trace(const uint8_t *in, int64_t n, int node_order, uint8_t *trace, int maxlen, uint32_t *len)
 {
-    static LineStack stk;
+    static host::LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
-        uint8_t buf[84] = {0};
-        memcpy(buf, in + i * 81, 81);
         uint32_t x[21];
-        for (int k = 0; k < 21; ++k)
-            x[k] = (uint32_t)buf[4 * k] | ((uint32_t)buf[4 * k + 1] << 8) | ((uint32_t)buf[4 * k + 2] << 16) |
-                   ((uint32_t)buf[4 * k + 3] << 24);
+        host::words_of(in + i * 81, x);
         plane::Board B;
         bool clash = false;
         len[i] = 0;
@@ -103,14 +83,10 @@ static int mrv_pick(const plane::Board &B, const uint32_t und[3], int &band, int
 
 extern "C" void mrv_count(const uint8_t *in, int64_t n, uint32_t *passes, uint32_t *guesses, int32_t *count)
 {
-    static HostStack stk;
+    static host::LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
-        uint8_t buf[84] = {0};
-        memcpy(buf, in + i * 81, 81);
         uint32_t x[21];
-        for (int k = 0; k < 21; ++k)
-            x[k] = (uint32_t)buf[4 * k] | ((uint32_t)buf[4 * k + 1] << 8) | ((uint32_t)buf[4 * k + 2] << 16) |
-                   ((uint32_t)buf[4 * k + 3] << 24);
+        host::words_of(in + i * 81, x);
         plane::Board B;
         bool clash = false;
         passes[i] = guesses[i] = 0;

@@ -2,23 +2,9 @@
 // the host) for scripts/order_sim.py: can a board's pass count be predicted
 // before it is solved, and would a heavy-first board order shorten the end of
 // a launch?  Tooling only.
-#include <stdint.h>
-#include <string.h>
-#include "../../sudoku_solver_distributed_amd/csrc/plane_solver.h"
+#include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
 
-struct HostStack {
-    uint32_t w[82 * plane::STACK_WORDS];
-    void put(uint32_t d, int k, uint32_t v) { w[d * plane::STACK_WORDS + k] = v; }
-    uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_WORDS + k]; }
-};
-
-static void words_of(const uint8_t *src, uint32_t x[21])
-{
-    uint8_t buf[84] = {0};
-    memcpy(buf, src, 81);
-    for (int k = 0; k < 21; ++k)
-        x[k] = buf[4 * k] | (buf[4 * k + 1] << 8) | (buf[4 * k + 2] << 16) | ((uint32_t)buf[4 * k + 3] << 24);
-}
+using host::words_of;
 
 static void count_open(const plane::Board &B, const uint32_t und[3], int &U, int &cs, int &bi)
 {
@@ -38,7 +24,7 @@ static void count_open(const plane::Board &B, const uint32_t und[3], int &U, int
 // and pass result after k + 1 passes
 extern "C" void root_features(const uint8_t *in, int64_t n, uint32_t mrv_after, int32_t *out)
 {
-    static HostStack stk;
+    static host::LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
         uint32_t x[21];
         words_of(in + i * 81, x);

@@ -7,7 +7,7 @@ soffset is an inline constant, so a buffer_store_dwordx4 with a REGISTER
 soffset (offset > 64 bytes) can be followed at once by a VALU write of its
 data.  In the plane kernel's stack push that corrupted search levels (~0.65 %
 of boards ended UNSOLVABLE); the push now keeps its data live through an
-s_nop (plane_kernel.h PlaneStack::push).
+s_nop (plane_stack.h PlaneStack::push).
 
 The scan looks at every instruction issued inside the hazard window: an
 instruction is one wait state, `s_nop N` is N + 1; a VALU write of a data

@@ -2,7 +2,7 @@
 // canon_kernel, canon_reduce_kernel and their C ABI entries
 // (sdk_canonical_scratch_bytes, sdk_canonical_batch).  A unit of its own:
 // the solve and count kernels' units, their flags and their workspace are
-// not involved.
+// not involved (common.h is included for cached_occupancy alone).
 //
 // canon_kernel: one workgroup of four waves per (board, slice).  Slice s of S
 // is the row variants [s*2592/S, (s+1)*2592/S).  The board and its transpose
@@ -29,12 +29,7 @@
 // Scratch: n * S records of 64 bytes, board-major; every record is written
 // by the first kernel before the second reads it, so its contents at the
 // call do not matter.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <atomic>
-
-#include "../../include/sudoku_hip.h"
+#include "common.h"
 #include "canon.h"
 
 #define CANON_THREADS 256
@@ -197,13 +192,7 @@ static std::atomic<int> g_canon_wgs{0};
 static int canon_slices(int64_t n, int slices)
 {
     if (slices > 0 || n <= 0) return slices;
-    int per_cu = g_canon_wgs.load();
-    if (!per_cu) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, canon_kernel, CANON_THREADS, 0) != hipSuccess ||
-            per_cu <= 0 || per_cu > CANON_WGS_PER_CU)
-            per_cu = CANON_WGS_PER_CU;
-        g_canon_wgs.store(per_cu);
-    }
+    const int per_cu = cached_occupancy(canon_kernel, CANON_THREADS, CANON_WGS_PER_CU, CANON_WGS_PER_CU, g_canon_wgs);
     const int64_t S = (int64_t)sdk_device_cu_count() * per_cu / n;
     return (int)(S < 1 ? 1 : S > CANON_AUTO_MAX_SLICES ? CANON_AUTO_MAX_SLICES : S);
 }

@@ -1,11 +1,14 @@
-// common.h -- definitions shared by the two translation units
+// common.h -- definitions shared by the four translation units
 // (sudoku_kernels.hip: wave-per-board kernel, check / task / frontier kernels
-// and the C ABI; plane_kernels.hip: the lane-per-board digit-plane kernel).
+// and the C ABI; plane_kernels.hip: the lane-per-board digit-plane kernel;
+// count_kernels.hip and canon_kernels.hip: the launch-sizing helper only).
 #ifndef SDK_COMMON_H
 #define SDK_COMMON_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "../../include/sudoku_hip.h"
 
@@ -78,6 +81,20 @@ __device__ __forceinline__ int order_cell(uint64_t eb0, uint64_t eb1, int order)
     if (start >= 64) return start + __builtin_ctzll(eb1 >> (start - 64));
     const uint64_t m = eb0 & (~0ull << start);
     return m ? __builtin_ctzll(m) : 64 + __builtin_ctzll(eb1);
+}
+
+// Workgroups of `kernel` (`block` threads each) that one CU holds at once:
+// asked of the runtime once and kept in `cache`; `fallback` where the query
+// fails, never more than `cap`.
+template <typename K>
+static inline int cached_occupancy(K kernel, int block, int fallback, int cap, std::atomic<int> &cache)
+{
+    int nb = cache.load();
+    if (nb) return nb;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0) != hipSuccess || nb <= 0) nb = fallback;
+    if (nb > cap) nb = cap;
+    cache.store(nb);
+    return nb;
 }
 
 // Several batches in one plane launch (sdk_solve_batches): the queue hands

@@ -1,7 +1,8 @@
 // count_kernels.hip -- translation unit of the batched, capped completion
 // count (plane_count.h): count_kernel and its C ABI entries
 // (sdk_count_scratch_bytes, sdk_count_solutions_batch).  A unit of its own:
-// the solve kernels' units, their flags and their workspace are not involved.
+// the solve kernels' units, their flags and their workspace are not involved
+// (common.h is included for cached_occupancy alone).
 //
 // count_kernel: one board per LANE, persistent one-wave workgroups.  A lane
 // holds its board's 27 plane words, und[] / nd[] (plane::pass_ahead), its
@@ -18,17 +19,14 @@
 //
 // Scratch: [0, 256) the queue head's block (zeroed by the call itself, in
 // stream order, before the kernel), then per wave 64 lanes x COUNT_MAX_DEPTH
-// stack lines of 128 bytes in the layout plane_kernel.h's PlaneStack
-// documents (words 0..26 planes, 27 entry, 28..30 und[], 31 unused).  Each
-// wave addresses its own lines through a buffer descriptor that covers
-// exactly them, so a bad level could never reach another wave's lines.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <atomic>
-
-#include "../../include/sudoku_hip.h"
+// stack lines of 128 bytes, pushed and popped by plane_stack.h's PlaneStack
+// (words 0..26 planes, 27 entry, 28..30 und[], 31 unused; level L of a lane
+// at lane_off + 128 L).  Each wave addresses its own lines through a buffer
+// descriptor that covers exactly them, so a bad level could never reach
+// another wave's lines.
+#include "common.h"
 #include "plane_count.h"
+#include "plane_stack.h"
 
 #define COUNT_THREADS 64    // one wave per workgroup
 #define COUNT_WAVES_PER_EU 4
@@ -43,66 +41,6 @@
 #define COUNT_LANE_BYTES ((uint32_t)plane::COUNT_MAX_DEPTH * 128u)
 #define COUNT_WAVE_BYTES (64u * COUNT_LANE_BYTES)
 #define COUNT_NONE INT32_MIN  // a lane with no result to write
-
-typedef uint32_t cnt_v4u __attribute__((ext_vector_type(4)));
-
-// The lane's stack lines (level L at lane_off + 128 L within the wave's
-// descriptor).  A push or pop is 8 dwordx4 accesses to one line.
-struct CountStack {
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t lane_off;
-    __device__ __forceinline__ int voff(uint32_t level) const { return (int)(lane_off + level * 128u); }
-    __device__ __forceinline__ void push(uint32_t level, plane::Board &B, const uint32_t (&und)[3],
-                                         uint32_t entry) const
-    {
-        const int v = voff(level);
-        plane::pin_board(B);
-#define CQ(a, b, c, d) (cnt_v4u){B.P[a / 3][a % 3], B.P[b / 3][b % 3], B.P[c / 3][c % 3], B.P[d / 3][d % 3]}
-        const cnt_v4u q0 = CQ(0, 1, 2, 3), q1 = CQ(4, 5, 6, 7), q2 = CQ(8, 9, 10, 11), q3 = CQ(12, 13, 14, 15),
-                      q4 = CQ(16, 17, 18, 19), q5 = CQ(20, 21, 22, 23),
-                      q6 = (cnt_v4u){B.P[8][0], B.P[8][1], B.P[8][2], entry},
-                      q7 = (cnt_v4u){und[0], und[1], und[2], 0u};
-#undef CQ
-        __builtin_amdgcn_raw_buffer_store_b128(q0, rsrc, v, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q1, rsrc, v, 16, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q2, rsrc, v, 32, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q3, rsrc, v, 48, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q4, rsrc, v, 64, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q5, rsrc, v, 80, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q6, rsrc, v, 96, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(q7, rsrc, v, 112, 0);
-        // a dwordx4 store reads its data registers after issue, and hipcc does
-        // not always pad a following VALU write of them (PlaneStack::push,
-        // scripts/store_hazard_check.py): all eight quads stay live through
-        // two wait states
-        asm volatile("s_nop 1" ::"v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(q4), "v"(q5), "v"(q6), "v"(q7));
-    }
-    __device__ __forceinline__ uint32_t pop(uint32_t level, plane::Board &B, uint32_t (&und)[3]) const
-    {
-        const int v = voff(level);
-        const cnt_v4u q0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 0, 0);
-        const cnt_v4u q1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 16, 0);
-        const cnt_v4u q2 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 32, 0);
-        const cnt_v4u q3 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 48, 0);
-        const cnt_v4u q4 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 64, 0);
-        const cnt_v4u q5 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 80, 0);
-        const cnt_v4u t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 96, 0);
-        const cnt_v4u u = __builtin_amdgcn_raw_buffer_load_b128(rsrc, v, 112, 0);
-        und[0] = u.x; und[1] = u.y; und[2] = u.z;
-        B.P[0][0] = q0.x; B.P[0][1] = q0.y; B.P[0][2] = q0.z; B.P[1][0] = q0.w;
-        B.P[1][1] = q1.x; B.P[1][2] = q1.y; B.P[2][0] = q1.z; B.P[2][1] = q1.w;
-        B.P[2][2] = q2.x; B.P[3][0] = q2.y; B.P[3][1] = q2.z; B.P[3][2] = q2.w;
-        B.P[4][0] = q3.x; B.P[4][1] = q3.y; B.P[4][2] = q3.z; B.P[5][0] = q3.w;
-        B.P[5][1] = q4.x; B.P[5][2] = q4.y; B.P[6][0] = q4.z; B.P[6][1] = q4.w;
-        B.P[6][2] = q5.x; B.P[7][0] = q5.y; B.P[7][1] = q5.z; B.P[7][2] = q5.w;
-        B.P[8][0] = t.x; B.P[8][1] = t.y; B.P[8][2] = t.z;
-        return t.w;
-    }
-    __device__ __forceinline__ void put_entry(uint32_t level, uint32_t entry) const
-    {
-        __builtin_amdgcn_raw_buffer_store_b32(entry, rsrc, voff(level), 108, 0);
-    }
-};
 
 // The 21 words of the board at `src` (any alignment): the 21 aligned dwords
 // that hold its 81 bytes (byte 80 lies in dword 20 for every alignment, so
@@ -128,7 +66,7 @@ __global__ __launch_bounds__(COUNT_THREADS, COUNT_WAVES_PER_EU) void count_kerne
     int32_t limit, unsigned long long *__restrict__ head, uint8_t *__restrict__ stack)
 {
     const int lane = threadIdx.x;
-    const CountStack stk = {__builtin_amdgcn_make_buffer_rsrc(stack + (size_t)blockIdx.x * COUNT_WAVE_BYTES, 0,
+    const PlaneStack stk = {__builtin_amdgcn_make_buffer_rsrc(stack + (size_t)blockIdx.x * COUNT_WAVE_BYTES, 0,
                                                               (int)COUNT_WAVE_BYTES, 0x00020000),
                             (uint32_t)lane * COUNT_LANE_BYTES};
     plane::Board B;
@@ -200,14 +138,8 @@ static std::atomic<int> g_count_bpc{0};
 // waves of a full grid on the current device: every CU at the kernel's occupancy
 static int64_t count_full_waves()
 {
-    int nb = g_count_bpc.load();
-    if (!nb) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, count_kernel, COUNT_THREADS, 0) != hipSuccess || nb <= 0)
-            nb = 4 * COUNT_WAVES_PER_EU;
-        if (nb > 4 * COUNT_WAVES_PER_EU) nb = 4 * COUNT_WAVES_PER_EU;  // four SIMDs per CU
-        g_count_bpc.store(nb);
-    }
-    return (int64_t)sdk_device_cu_count() * nb;
+    const int per_cu = 4 * COUNT_WAVES_PER_EU;  // four SIMDs per CU
+    return (int64_t)sdk_device_cu_count() * cached_occupancy(count_kernel, COUNT_THREADS, per_cu, per_cu, g_count_bpc);
 }
 
 static int64_t count_waves(int64_t n, int max_waves)

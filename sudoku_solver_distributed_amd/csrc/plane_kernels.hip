@@ -112,9 +112,6 @@ hipError_t sdk_launch_plane_multi(const PlaneBatches &bs, unsigned long long *ws
 
 int sdk_plane_blocks_per_cu()
 {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, plane_kernel, PLANE_THREADS, 0) != hipSuccess || nb <= 0)
-        nb = 4;
-    const int cap = 32 * 64 / PLANE_THREADS;  // 32 waves per CU
-    return nb > cap ? cap : nb;
+    static std::atomic<int> cache{0};
+    return cached_occupancy(plane_kernel, PLANE_THREADS, 4, 32 * 64 / PLANE_THREADS /* 32 waves per CU */, cache);
 }

@@ -501,19 +501,7 @@ static int cu_count()
     return g_cu_count[dev];
 }
 
-template <typename K>
-static int blocks_per_cu(K kernel, std::atomic<int> &cached)
-{
-    int v = cached.load();
-    if (v) return v;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, BLOCK_THREADS, 0) != hipSuccess || nb <= 0)
-        nb = 4;
-    if (nb > 8) nb = 8;
-    cached.store(nb);
-    return nb;
-}
-static std::atomic<int> g_bpc_packed{0}, g_bpc_plane{0};
+static std::atomic<int> g_bpc_packed{0};
 
 // waves of the deferred-board kernels after a plane launch: one workgroup
 // (4 waves) per CU.  The count of deferred boards is known only on the
@@ -527,8 +515,7 @@ static int64_t deferred_waves() { return (int64_t)cu_count() * WAVES_PER_BLOCK; 
 // their stacks (the workspace holds them after WS_STACK_BYTE)
 static int64_t plane_max_threads()
 {
-    if (!g_bpc_plane.load()) g_bpc_plane.store(sdk_plane_blocks_per_cu());
-    return (int64_t)cu_count() * g_bpc_plane.load() * PLANE_THREADS;
+    return (int64_t)cu_count() * sdk_plane_blocks_per_cu() * PLANE_THREADS;
 }
 static size_t plane_stack_bytes(int64_t threads)
 {
@@ -622,7 +609,7 @@ int sdk_solve_batch_grid(const uint8_t *d_puzzles, uint8_t *d_solutions, int32_t
     std::lock_guard<std::mutex> lk(g_launch_mu);
     hipError_t e;
     if (variant == SDK_KERNEL_PACKED) {
-        const int64_t max_waves = (int64_t)cu_count() * blocks_per_cu(solvep_kernel, g_bpc_packed) * WAVES_PER_BLOCK;
+        const int64_t max_waves = (int64_t)cu_count() * cached_occupancy(solvep_kernel, BLOCK_THREADS, 4, 8, g_bpc_packed) * WAVES_PER_BLOCK;
         // A batch the static hand-out covers (one board per wave) never uses
         // the queue head's value, and an unordered one not the best word:
         // no re-arm launch then (a single board's latency: -1 launch)

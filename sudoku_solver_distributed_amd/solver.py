@@ -155,6 +155,24 @@ class BatchSolver:
             t = t.to(self.device)
         return t.contiguous()
 
+    def _scratch(self, attr: str, need: int) -> torch.Tensor:
+        """The cached scratch tensor `attr`, grown to `need` bytes (caller
+        holds self._lock)."""
+        sc = getattr(self, attr)
+        if sc is None or sc.numel() < need:
+            if sc is not None and self._last_stream is not None:
+                sc.record_stream(self._last_stream)  # a call may still be running on it
+            sc = torch.empty(max(need, 64), dtype=torch.uint8, device=self.device)
+            setattr(self, attr, sc)
+        return sc
+
+    @staticmethod
+    def _rc_only(rc: int, what: str) -> None:
+        """Raise for an entry that reports by return code only (it does not
+        set sdk_last_error)."""
+        if rc != 0:
+            raise SudokuHipError(f"{what} failed ({rc}): " + ("HIP error" if rc == -1 else "bad arguments"))
+
     # -------------------------------------------------------------- solve
     def solve(self, puzzles, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
               ordered: bool = False, order="gen", stream=None, grid_waves: int = 0, pipelined: bool = False
@@ -207,18 +225,11 @@ class BatchSolver:
         counts = torch.empty(n, dtype=torch.int32, device=self.device)
         first = torch.empty_like(p) if return_first else None
         with self._lock, torch.cuda.device(self.device):
-            need = int(self.lib.sdk_count_scratch_bytes(n, int(max_waves)))
-            sc = self._count_scratch
-            if sc is None or sc.numel() < need:
-                if sc is not None and self._last_stream is not None:
-                    sc.record_stream(self._last_stream)  # a count may still be running on it
-                sc = self._count_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            sc = self._scratch("_count_scratch", int(self.lib.sdk_count_scratch_bytes(n, int(max_waves))))
             rc = self.lib.sdk_count_solutions_batch(p.data_ptr(), counts.data_ptr(),
                                                     first.data_ptr() if return_first else None, n, limit,
                                                     sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
-        if rc != 0:  # (reported by return code only: the entry does not set sdk_last_error)
-            raise SudokuHipError(f"sdk_count_solutions_batch failed ({rc}): "
-                                 + ("HIP error" if rc == -1 else "bad arguments"))
+        self._rc_only(rc, "sdk_count_solutions_batch")
         return (counts, first) if return_first else counts
 
     # ---------------------------------------------------------- canonical
@@ -247,18 +258,11 @@ class BatchSolver:
         sym = torch.empty(n, dtype=torch.int32, device=self.device)
         autos = torch.empty(n, dtype=torch.int32, device=self.device) if return_autos else None
         with self._lock, torch.cuda.device(self.device):
-            need = int(self.lib.sdk_canonical_scratch_bytes(n, slices))
-            sc = self._canon_scratch
-            if sc is None or sc.numel() < need:
-                if sc is not None and self._last_stream is not None:
-                    sc.record_stream(self._last_stream)  # a call may still be running on it
-                sc = self._canon_scratch = torch.empty(max(need, 64), dtype=torch.uint8, device=self.device)
+            sc = self._scratch("_canon_scratch", int(self.lib.sdk_canonical_scratch_bytes(n, slices)))
             rc = self.lib.sdk_canonical_batch(p.data_ptr(), canon.data_ptr(), sym.data_ptr(),
                                               autos.data_ptr() if return_autos else None, n, slices,
                                               sc.data_ptr(), sc.numel(), self._ws_stream(stream))
-        if rc != 0:  # (reported by return code only: the entry does not set sdk_last_error)
-            raise SudokuHipError(f"sdk_canonical_batch failed ({rc}): "
-                                 + ("HIP error" if rc == -1 else "bad arguments"))
+        self._rc_only(rc, "sdk_canonical_batch")
         out = (canon,) + ((sym,) if return_sym else ()) + ((autos,) if return_autos else ())
         return out if len(out) > 1 else canon
 

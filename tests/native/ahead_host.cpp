@@ -1,82 +1,40 @@
 // Host build of the look-ahead path of
 // sudoku_solver_distributed_amd/csrc/plane_solver.h (pass_ahead,
-// search_step_ahead, solve_ahead: what the plane kernel's lane loop runs) for
-// the CPU test-suite (tests/test_pass_ahead.py): checked pass by pass against
-// plane::pass, and as a solver against plane::solve, the oracle and the
-// wave-wide solver's continuation.  Not a product path.
-#include <stdint.h>
-#include <string.h>
+// search_step_ahead: what the plane kernel's lane loop runs) for the CPU
+// test-suite (tests/test_pass_ahead.py): checked pass by pass against
+// plane::pass, and as a solver (host_model.h's driver) against the same
+// driver on plane::pass, the oracle and the wave-wide solver's continuation.
+// Not a product path.
+#include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
 
-#include "../../sudoku_solver_distributed_amd/csrc/plane_wide.h"
+using host::words_of;
 
-enum { LEVEL_WORDS = plane::STACK_LINE_WORDS, MAX_LEVELS = 82 };
-
-// plane_kernel's per-lane stack line: word 3d+b = P[d][b], word 27 = entry,
-// words 28-30 = the level's undetermined cells (the lane path only)
-static uint32_t stack_words[MAX_LEVELS * LEVEL_WORDS];
-struct LineStack {
-    void put(uint32_t level, int k, uint32_t v) { stack_words[level * LEVEL_WORDS + k] = v; }
-    uint32_t get(uint32_t level, int k) const { return stack_words[level * LEVEL_WORDS + k]; }
-};
-static LineStack lines;
-
-// the wave-wide solver's view of the same lines: it never reads words 28-30
-struct WStack {
-    uint32_t *w;
-    void push(uint32_t level, const wide::V &v, const wide::Lanes &L, uint32_t entry) const
-    {
-        for (int i = 0; i < 64; ++i)
-            if ((L.valid.m >> i) & 1) w[level * LEVEL_WORDS + L.word.x[i]] = v.x[i];
-        w[level * LEVEL_WORDS + plane::STACK_ENTRY] = entry;
-    }
-    uint32_t entry(uint32_t level) const { return w[level * LEVEL_WORDS + plane::STACK_ENTRY]; }
-    wide::V restore(uint32_t level, const wide::Lanes &L) const
-    {
-        wide::V r(0u);
-        for (int i = 0; i < 64; ++i)
-            if ((L.valid.m >> i) & 1) r.x[i] = w[level * LEVEL_WORDS + L.word.x[i]];
-        return r;
-    }
-    void put_entry(uint32_t level, uint32_t e) const { w[level * LEVEL_WORDS + plane::STACK_ENTRY] = e; }
-};
-
-static void words_of(const uint8_t *src, uint32_t (&x)[21])
-{
-    uint8_t buf[84] = {0};
-    memcpy(buf, src, 81);
-    for (int k = 0; k < 21; ++k)
-        x[k] = (uint32_t)buf[4 * k] | ((uint32_t)buf[4 * k + 1] << 8) | ((uint32_t)buf[4 * k + 2] << 16) |
-               ((uint32_t)buf[4 * k + 3] << 24);
-}
-
-// Solve each board with plane::solve (ahead = 0) or plane::solve_ahead (1).
-// status: 1 solved, 0 no completion, -1 invalid byte, 2 left to the wave
-// kernel (clashing givens or depth overflow).
+// The lane solver alone (host_model.h's driver): on plane::pass (ahead = 0)
+// or on the look-ahead pass (1).  status: 1 solved, 0 no completion, -1
+// invalid byte, 2 left to the wave kernel (clashing givens or depth overflow).
 extern "C" void ahead_solve_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_t n, int node_order,
                                   uint32_t max_depth, uint32_t mrv_after, int ahead, uint64_t *guesses,
                                   uint64_t *passes)
 {
-    uint64_t g = 0, p = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *src = in + i * 81;
-        uint8_t *dst = out + i * 81;
-        uint32_t x[21];
-        words_of(src, x);
-        plane::Board B;
-        bool clash = false;
-        memcpy(dst, src, 81);
-        if (!plane::load_words(B, x, clash)) { status[i] = -1; continue; }
-        if (clash) { status[i] = 2; continue; }
-        plane::Stats st = {0, 0};
-        const int r = ahead ? plane::solve_ahead(B, lines, node_order, max_depth, st, mrv_after)
-                            : plane::solve(B, lines, node_order, max_depth, st, mrv_after);
-        g += st.guesses;
-        p += st.passes;
-        if (r == 1) plane::store_values(B, [&](int c, uint32_t v) { dst[c] = (uint8_t)v; });
-        status[i] = r == 1 ? 1 : r == 0 ? 0 : 2;
-    }
-    *guesses = g;
-    *passes = p;
+    host::Counts c;
+    host::solve_batch(in, out, status, n, ahead != 0, host::LANE_ONLY, node_order, max_depth, mrv_after, c);
+    *guesses = c.guesses;
+    *passes = c.passes_lane;
+}
+
+// `lane_guesses` guesses (or the whole search, if it ends first) on the
+// look-ahead lane path, stepping exactly like plane_kernel, then the rest of
+// the search on the wave-wide solver from the same planes, stack and depth
+// (und / nd dropped, as the kernel's tail records drop them).  Statuses as
+// ahead_solve_batch.
+extern "C" void ahead_wide_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_t n, int node_order,
+                                 uint32_t max_depth, uint32_t mrv_after, uint32_t lane_guesses, uint64_t *passes_lane,
+                                 uint64_t *passes_wide)
+{
+    host::Counts c;
+    host::solve_batch(in, out, status, n, true, lane_guesses, node_order, max_depth, mrv_after, c);
+    *passes_lane = c.passes_lane;
+    *passes_wide = c.passes_wide;
 }
 
 // ---- lock-step: pass_ahead against plane::pass
@@ -193,84 +151,4 @@ extern "C" int64_t ahead_check_pass(const uint8_t *in, int64_t n, int64_t nrand,
         }
     }
     return bad;
-}
-
-// ---- hand-over to the wave-wide solver
-
-static wide::V to_wave(const plane::Board &B, const wide::Lanes &L)
-{
-    wide::V w(0u);
-    for (int i = 0; i < 64; ++i)
-        if ((L.valid.m >> i) & 1) w.x[i] = B.P[L.d.x[i]][L.b.x[i]];
-    return w;
-}
-
-static void store_wave(const wide::V &w, const wide::Lanes &L, uint8_t *dst)
-{
-    wide::V s[4];
-    wide::value_slices(w, L, s);
-    for (int c = 0; c < 81; ++c) {
-        const int b = plane::cell_band(c), p = plane::cell_pos(c);
-        uint32_t v = 0;
-        for (int k = 0; k < 4; ++k) v |= ((s[k].x[16 * b] >> p) & 1u) << k;
-        dst[c] = (uint8_t)v;
-    }
-}
-
-// `lane_guesses` guesses (or the whole search, if it ends first) on the
-// look-ahead lane path, stepping exactly like plane_kernel, then the rest of
-// the search on the wave-wide solver from the same planes, stack and depth
-// (und / nd dropped, as the kernel's tail records drop them).  Statuses as
-// ahead_solve_batch.
-extern "C" void ahead_wide_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_t n, int node_order,
-                                 uint32_t max_depth, uint32_t mrv_after, uint32_t lane_guesses, uint64_t *passes_lane,
-                                 uint64_t *passes_wide)
-{
-    const WStack stk = {stack_words};
-    const wide::Lanes L = wide::lanes();
-    uint64_t pl = 0, pw = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *src = in + i * 81;
-        uint8_t *dst = out + i * 81;
-        memcpy(dst, src, 81);
-        uint32_t x[21];
-        words_of(src, x);
-        plane::Board B;
-        bool clash = false;
-        uint32_t und[3], nd[3];
-        if (!plane::load_words(B, x, clash, nd)) { status[i] = -1; continue; }
-        if (clash) { status[i] = 2; continue; }
-        for (int b = 0; b < 3; ++b) und[b] = plane::ROWS & ~nd[b];  // as the kernel's refill: nd = the givens
-        uint32_t depth = 0, lg = 0, mst = 0;
-        int done = -2;  // -2: hand off
-        const plane::WordStack<LineStack> ls = {lines};
-        while (lg < lane_guesses) {
-            const int r = plane::pass_ahead(B, und, nd);
-            pl++;
-            const int s = plane::search_step_ahead(B, und, nd, r, depth, mst, ls, node_order, max_depth, mrv_after, lg);
-            if (s == plane::S_CONT) continue;
-            done = s == plane::S_SOLVED ? 1 : s == plane::S_NONE ? 0 : -1;
-            break;
-        }
-        if (done == 1) {
-            plane::store_values(B, [&](int c, uint32_t v) { dst[c] = (uint8_t)v; });
-            status[i] = 1;
-            continue;
-        }
-        if (done == 0) { status[i] = 0; continue; }
-        if (done == -1) { status[i] = 2; continue; }
-        wide::V w = to_wave(B, L);
-        wide::Stats st = {0, 0, 0};
-        wide::NoCancel hk;
-        const int r = wide::solve(w, depth, stk, L, node_order, max_depth, st, hk, mst, mrv_after);
-        pw += st.passes;
-        if (r == wide::W_SOLVED) {
-            store_wave(w, L, dst);
-            status[i] = 1;
-        } else {
-            status[i] = r == wide::W_UNSOLVABLE ? 0 : 2;
-        }
-    }
-    *passes_lane = pl;
-    *passes_wide = pw;
 }

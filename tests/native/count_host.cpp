@@ -2,30 +2,11 @@
 // completion count: count_step, count_iter, count_board -- what count_kernel's
 // lane loop runs) for the CPU test-suite (tests/test_count_host.py), checked
 // against the oracle's counter.  Not a product path.
-#include <stdint.h>
-#include <string.h>
-
+#include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
 #include "../../sudoku_solver_distributed_amd/csrc/plane_count.h"
 
-enum { LEVEL_WORDS = plane::STACK_LINE_WORDS, MAX_LEVELS = plane::COUNT_MAX_DEPTH };
-
-// count_kernel's per-lane stack line: word 3d+b = P[d][b], word 27 = entry,
-// words 28-30 = the level's undetermined cells
-static uint32_t stack_words[MAX_LEVELS * LEVEL_WORDS];
-struct LineStack {
-    void put(uint32_t level, int k, uint32_t v) { stack_words[level * LEVEL_WORDS + k] = v; }
-    uint32_t get(uint32_t level, int k) const { return stack_words[level * LEVEL_WORDS + k]; }
-};
-static LineStack lines;
-
-static void words_of(const uint8_t *src, uint32_t (&x)[21])
-{
-    uint8_t buf[84] = {0};
-    memcpy(buf, src, 81);
-    for (int k = 0; k < 21; ++k)
-        x[k] = (uint32_t)buf[4 * k] | ((uint32_t)buf[4 * k + 1] << 8) | ((uint32_t)buf[4 * k + 2] << 16) |
-               ((uint32_t)buf[4 * k + 3] << 24);
-}
+// count_kernel's per-lane stack lines
+static host::LineStack lines;
 
 // count[i] = min(limit, completions of board i), -1 for a byte > 9, 0 for
 // clashing givens, -3 if the search needed more than max_depth (<= 81)
@@ -35,12 +16,12 @@ extern "C" void count_host_batch(const uint8_t *in, int32_t *count, uint8_t *fir
                                  uint32_t max_depth, uint64_t *passes, uint32_t *deepest)
 {
     plane::CountStats st = {0, 0};
-    if (max_depth > (uint32_t)MAX_LEVELS) max_depth = MAX_LEVELS;
+    if (max_depth > (uint32_t)plane::COUNT_MAX_DEPTH) max_depth = plane::COUNT_MAX_DEPTH;
     for (int64_t i = 0; i < n; ++i) {
         const uint8_t *src = in + i * 81;
         uint8_t *dst = first ? first + i * 81 : nullptr;
         uint32_t x[21], given[3];
-        words_of(src, x);
+        host::words_of(src, x);
         plane::Board B;
         bool clash = false;
         int32_t c;

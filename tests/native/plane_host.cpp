@@ -1,56 +1,20 @@
 // Host build of sudoku_solver_distributed_amd/csrc/plane_solver.h for the CPU
 // test-suite (tests/test_plane_solver.py): the digit-plane lane solver is
 // checked against the oracle before the GPU runs it.  Not a product path.
-#include <stdint.h>
-#include <string.h>
-#include "../../sudoku_solver_distributed_amd/csrc/plane_solver.h"
+#include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
 
-struct HostStack {
-    uint32_t w[82 * plane::STACK_WORDS];
-    void put(uint32_t d, int k, uint32_t v) { w[d * plane::STACK_WORDS + k] = v; }
-    uint32_t get(uint32_t d, int k) const { return w[d * plane::STACK_WORDS + k]; }
-};
+using host::words_of;
 
-static void words_of(const uint8_t *src, uint32_t (&x)[21])
-{
-    uint8_t buf[84] = {0};
-    memcpy(buf, src, 81);
-    for (int k = 0; k < 21; ++k)
-        x[k] = (uint32_t)buf[4 * k] | ((uint32_t)buf[4 * k + 1] << 8) | ((uint32_t)buf[4 * k + 2] << 16) |
-               ((uint32_t)buf[4 * k + 3] << 24);
-}
-
-// the search-mode switch of plane::solve (0 = the walk only), for every
-// solve below
-static uint32_t g_mrv_after = 0;
-extern "C" void plane_set_mrv_after(uint32_t k) { g_mrv_after = k; }
-
-// status: 1 solved, 0 no completion, -1 invalid byte, 2 left to the wave
-// kernel (clashing givens or depth overflow)
+// the lane solver alone on plane::pass (host_model.h's driver).  status: 1
+// solved, 0 no completion, -1 invalid byte, 2 left to the wave kernel
+// (clashing givens or depth overflow)
 extern "C" void plane_solve_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_t n, int node_order,
-                                  uint32_t max_depth, uint64_t *guesses, uint64_t *passes)
+                                  uint32_t max_depth, uint32_t mrv_after, uint64_t *guesses, uint64_t *passes)
 {
-    static HostStack stk;
-    uint64_t g = 0, p = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *src = in + i * 81;
-        uint8_t *dst = out + i * 81;
-        uint32_t x[21];
-        words_of(src, x);
-        plane::Board B;
-        bool clash = false;
-        memcpy(dst, src, 81);
-        if (!plane::load_words(B, x, clash)) { status[i] = -1; continue; }
-        if (clash) { status[i] = 2; continue; }
-        plane::Stats st = {0, 0};
-        const int r = plane::solve(B, stk, node_order, max_depth, st, g_mrv_after);
-        g += st.guesses;
-        p += st.passes;
-        if (r == 1) plane::store_values(B, [&](int c, uint32_t v) { dst[c] = (uint8_t)v; });
-        status[i] = r == 1 ? 1 : r == 0 ? 0 : 2;
-    }
-    *guesses = g;
-    *passes = p;
+    host::Counts c;
+    host::solve_batch(in, out, status, n, false, host::LANE_ONLY, node_order, max_depth, mrv_after, c);
+    *guesses = c.guesses;
+    *passes = c.passes_lane;
 }
 
 // load_words against a plain per-byte loader; returns the number of boards
@@ -95,17 +59,10 @@ extern "C" int64_t plane_check_load(const uint8_t *in, int64_t n)
 
 // per-board passes / guesses / deepest stack level of the plane solver
 // (scripts/make_hard_search.py filters search-heavy boards with it)
-struct DepthStack {
-    HostStack s;
-    uint32_t max_depth = 0;
-    void put(uint32_t d, int k, uint32_t v) { s.put(d, k, v); if (d + 1 > max_depth) max_depth = d + 1; }
-    uint32_t get(uint32_t d, int k) const { return s.get(d, k); }
-};
-
 extern "C" void plane_solve_stats(const uint8_t *in, int64_t n, int node_order, int32_t *passes, int32_t *guesses,
                                   int32_t *depth)
 {
-    static DepthStack stk;
+    static host::LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
         uint32_t x[21];
         words_of(in + i * 81, x);
@@ -114,11 +71,11 @@ extern "C" void plane_solve_stats(const uint8_t *in, int64_t n, int node_order, 
         passes[i] = guesses[i] = depth[i] = -1;
         if (!plane::load_words(B, x, clash) || clash) continue;
         plane::Stats st = {0, 0};
-        stk.max_depth = 0;
-        plane::solve(B, stk, node_order, 81, st, g_mrv_after);
+        stk.deepest = 0;
+        plane::solve(B, stk, node_order, 81, st);
         passes[i] = (int32_t)st.passes;
         guesses[i] = (int32_t)st.guesses;
-        depth[i] = (int32_t)stk.max_depth;
+        depth[i] = (int32_t)stk.deepest;
     }
 }
 
@@ -324,7 +281,7 @@ extern "C" int64_t plane_check_pass(const uint8_t *in, int64_t n, int64_t nrand,
 // distribution the plane kernel's scheduling sees)
 extern "C" void plane_board_passes(const uint8_t *in, int64_t n, int node_order, uint32_t *passes, uint32_t *guesses)
 {
-    static HostStack stk;
+    static host::LineStack stk;
     for (int64_t i = 0; i < n; ++i) {
         uint32_t x[21];
         words_of(in + i * 81, x);
@@ -333,7 +290,7 @@ extern "C" void plane_board_passes(const uint8_t *in, int64_t n, int node_order,
         passes[i] = guesses[i] = 0;
         if (!plane::load_words(B, x, clash) || clash) continue;
         plane::Stats st = {0, 0};
-        plane::solve(B, stk, node_order, 81, st, g_mrv_after);
+        plane::solve(B, stk, node_order, 81, st);
         passes[i] = st.passes;
         guesses[i] = st.guesses;
     }

@@ -63,7 +63,7 @@ def test_solver_raises_without_gpu():
 def test_no_wide_store_data_hazard():
     """Every >64-bit store in the product kernels has a wait state before its
     data registers are rewritten (scripts/store_hazard_check.py: hipcc does
-    not pad buffer stores with a register soffset; plane_kernel.h
+    not pad buffer stores with a register soffset; plane_stack.h
     PlaneStack::push pads its own)."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "scripts"))

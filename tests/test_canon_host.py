@@ -1,22 +1,19 @@
 """CPU checks of the canonical form (csrc/canon.h, what canon_kernel's lanes
-and canon_reduce_kernel run): the header compiled for the host with g++
-(tests/native/canon_host.cpp) against the fixture tests/golden/canon_cases.json
+and canon_reduce_kernel run): the header compiled for the host
+(tests/native/canon_host.cpp, built by native_build.py) against the fixture tests/golden/canon_cases.json
 (made by the CPU tool scripts/hard17/hard17_search.c --canon, re-run here),
 against an independent numpy brute force for sym and autos, and the C ABI's
 argument checks through ctypes (no GPU).  Every check is an equality."""
-import ctypes
 import os
-import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
+from native_build import host_lib
 
-NATIVE = os.path.join(ROOT, "tests", "native")
-HOST_FLAGS = os.environ.get("SDK_HOST_CFLAGS", "").split()
 SYMMETRIES = 3359232
 
 
@@ -34,17 +31,8 @@ def cases():
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("canon")), "libcanon_host.so")
-    subprocess.check_call(["g++", "-O2", "-fopenmp", "-shared", "-fPIC", "-std=c++17", *HOST_FLAGS, "-o", out,
-                           os.path.join(NATIVE, "canon_host.cpp")])
-    lib = ctypes.CDLL(out)
-    vp = ctypes.c_void_p
-    lib.canon_host_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int]
-    lib.canon_host_batch.restype = None
-    lib.canon_host_slice.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
-    lib.canon_host_slice.restype = None
-    return lib
+def host():
+    return host_lib("canon_host", openmp=True)
 
 
 def _canon(lib, boards, S=1):

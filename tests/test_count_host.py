@@ -1,31 +1,21 @@
 """CPU checks of the capped completion count (csrc/plane_count.h, what
-count_kernel's lanes run): the header compiled for the host with g++
-(tests/native/count_host.cpp) against the oracle's counter on the sets of
+count_kernel's lanes run): the header compiled for the host
+(tests/native/count_host.cpp, built by native_build.py) against the oracle's counter on the sets of
 count_cases.py, and the C ABI's argument checks through ctypes (no GPU)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import count_cases as C
+from native_build import host_lib
 
-NATIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
-HOST_FLAGS = os.environ.get("SDK_HOST_CFLAGS", "").split()
 COMPILED_DEPTH = 81  # plane::COUNT_MAX_DEPTH
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("count")), "libcount_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", *HOST_FLAGS, "-o", out,
-                           os.path.join(NATIVE, "count_host.cpp")])
-    lib = ctypes.CDLL(out)
-    lib.count_host_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    lib.count_host_batch.restype = None
-    return lib
+def host():
+    return host_lib("count_host")
 
 
 def _count(lib, boards, limit, first=True, max_depth=COMPILED_DEPTH, stats=None):

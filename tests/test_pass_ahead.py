@@ -1,40 +1,26 @@
 """CPU checks of the look-ahead pass (csrc/plane_solver.h: pass_ahead,
-search_step_ahead, solve_ahead -- what the plane kernel's lane loop runs):
+search_step_ahead -- what the plane kernel's lane loop runs):
 rule A moved from the head of a pass to its tail, so a pass reports DEAD and
 STUCK itself instead of leaving it to one more pass.  The header compiled for
-the host with g++ (tests/native/ahead_host.cpp): pass by pass against
-plane::pass, as a solver against plane::solve and the oracle, handed over to
-the wave-wide solver, and for the passes it saves."""
+the host (tests/native/ahead_host.cpp over csrc/host_model.h): pass by pass
+against plane::pass, as a solver against the plane::pass solver and the
+oracle, handed over to the wave-wide solver, and for the passes it saves."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, b81
+from native_build import host_lib
 from oracle import oracle as O
 
-NATIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
-HOST_FLAGS = os.environ.get("SDK_HOST_CFLAGS", "").split()
 FULL = "897124635531679284642385179154293867289716453376458912923867541765941328418532796"
 
 
 @pytest.fixture(scope="module")
-def ahead(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("ahead")), "libahead_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", *HOST_FLAGS, "-o", out,
-                           os.path.join(NATIVE, "ahead_host.cpp")])
-    lib = ctypes.CDLL(out)
-    lib.ahead_solve_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                      ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
-                                      ctypes.c_void_p, ctypes.c_void_p]
-    lib.ahead_check_pass.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64]
-    lib.ahead_check_pass.restype = ctypes.c_int64
-    lib.ahead_wide_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                     ctypes.c_void_p, ctypes.c_void_p]
-    return lib
+def ahead():
+    return host_lib("ahead_host")
 
 
 def _solve(lib, boards, ahead, node_order=0, mrv_after=0, max_depth=81, stats=None):

@@ -5,18 +5,14 @@ header (csrc/peer_greedy.h, compiled for the host) against the oracle, and
 -m gpu: sdk_peer_solve_batch against both.  The same for ONE node serving
 requests in a row (its partial_solution / tried sets carry over, node.py:149,
 167): tests/golden/golden_peer_seq.json, sdk_peer_solve_seq."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import b81, load_golden
+from native_build import host_lib
 from oracle import oracle as O
 
-NATIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
 STATUS = {1: 1, 0: 0, -1: 2}  # oracle -> peer_greedy.h status
 
 
@@ -46,14 +42,8 @@ def test_oracle_matches_reference_fixture():
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("peer")), "libpeer_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", "-o", so,
-                           os.path.join(NATIVE, "peer_host.cpp")])
-    lib = ctypes.CDLL(so)
-    lib.peer_host_batch.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64]
-    lib.peer_host_seq.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
-    return lib
+def host():
+    return host_lib("peer_host")
 
 
 def test_device_loop_matches_oracle_on_host(host):

@@ -1,55 +1,37 @@
 """CPU checks of the digit-plane lane solver (csrc/plane_solver.h, the
-default GPU solve kernel): the same header compiled for the host with g++
-(tests/native/plane_host.cpp), compared with the oracle on the goldens,
-generated boards in both walk orders, clashing givens, hard 17-clue boards,
+default GPU solve kernel): the same header compiled for the host
+(tests/native/plane_host.cpp over csrc/host_model.h, built by
+native_build.py), compared with the oracle on the goldens, generated boards in both walk orders, clashing givens, hard 17-clue boards,
 and its board loader against a plain per-byte loader."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import b81, load_golden
+from native_build import host_lib
 from oracle import oracle as O
-
-NATIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
-# extra compiler flags for the host builds, e.g. SDK_HOST_CFLAGS="-DSDK_PLANE_LC=7"
-# to check a rule-D variant against its restatement
-HOST_FLAGS = os.environ.get("SDK_HOST_CFLAGS", "").split()
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("plane")), "libplane_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", *HOST_FLAGS, "-o", out,
-                           os.path.join(NATIVE, "plane_host.cpp")])
-    lib = ctypes.CDLL(out)
-    lib.plane_solve_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                      ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    lib.plane_check_load.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    lib.plane_check_load.restype = ctypes.c_int64
-    lib.plane_set_mrv_after.argtypes = [ctypes.c_uint32]
-    lib.plane_set_mrv_after(0)
-    return lib
+def host():
+    return host_lib("plane_host")
 
 
 @pytest.fixture(params=[0, 1, 24, 128], ids=lambda k: f"mrv{k}")
-def mrv_after(request, host):
-    """plane::solve's search-mode switch (M_WALK -> M_COUNT after k passes,
-    0 = never): results never depend on it."""
-    host.plane_set_mrv_after(request.param)
-    yield request.param
-    host.plane_set_mrv_after(0)
+def mrv_after(request):
+    """The search-mode switch (M_WALK -> M_COUNT after k passes, 0 = never):
+    results never depend on it."""
+    return request.param
 
 
-def _solve(lib, boards, node_order=0, max_depth=81, stats=None):
+def _solve(lib, boards, node_order=0, max_depth=81, mrv_after=0, stats=None):
     boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
     out = np.zeros_like(boards)
     st = np.zeros(len(boards), dtype=np.int32)
     g, p = ctypes.c_uint64(), ctypes.c_uint64()
     lib.plane_solve_batch(boards.ctypes.data, out.ctypes.data, st.ctypes.data, len(boards), node_order,
-                          max_depth, ctypes.byref(g), ctypes.byref(p))
+                          max_depth, mrv_after, ctypes.byref(g), ctypes.byref(p))
     if stats is not None:
         stats.update(guesses=g.value, passes=p.value)
     return out, st
@@ -94,7 +76,7 @@ def test_plane_generated_vs_literal_walk(host, order, mrv_after):
     dup = "88" + full[2:30] + "0" + full[31:50] + "0" + full[51:70] + "0" + full[71:]
     edge = np.array([b81(x) for x in (full, "5" * 81, dup, "0" * 81)], dtype=np.uint8)
     puzzles = np.concatenate([grids, edge])
-    out, st = _solve(host, puzzles, node_order=int(order == "node"))
+    out, st = _solve(host, puzzles, node_order=int(order == "node"), mrv_after=mrv_after)
     want, wst = O.solve_batch(puzzles, order=order)
     mine = st != 2
     assert st[-3] == 2 and st[-2] == 2  # "5"*81 and dup have clashing givens
@@ -107,7 +89,7 @@ def test_plane_hard17_vs_oracle(host, order, mrv_after):
     from sudoku_solver_distributed_amd.gen import hard17_batch
     boards = hard17_batch(256, seed=7).numpy()
     stats = {}
-    out, st = _solve(host, boards, node_order=int(order == "node"), stats=stats)
+    out, st = _solve(host, boards, node_order=int(order == "node"), mrv_after=mrv_after, stats=stats)
     want, cnt = O.solve_unique_batch(boards)  # unique completions: every walk finds it
     assert (cnt == 1).all()
     assert (st == 1).all()
@@ -127,7 +109,7 @@ def test_plane_count_mode_unsolvable_and_multi(host, order, mrv_after):
     for i in range(len(b)):
         c = rng.choice(np.nonzero(b[i] == 0)[0])
         b[i, c] = 1 + (sols[i, c] + rng.integers(0, 8)) % 9  # a digit the completion does not hold
-    out, st = _solve(host, b, node_order=int(order == "node"))
+    out, st = _solve(host, b, node_order=int(order == "node"), mrv_after=mrv_after)
     # no completion by construction: one would also complete the unique
     # 17-clue board, whose completion does not hold the added digit
     mine = st != 2
@@ -168,8 +150,6 @@ def test_pass_matches_previous_formulation(host):
     rng = np.random.default_rng(13)
     for g in grids:  # gen.py-style: complete grids with 50 cells erased
         g[rng.choice(81, 50, replace=False)] = 0
-    host.plane_check_pass.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64]
-    host.plane_check_pass.restype = ctypes.c_int64
     boards = np.ascontiguousarray(np.concatenate([hard17_batch(300, seed=11).numpy(),
                                                   hard_search_batch(300, seed=12).numpy(),
                                                   grids]))
@@ -179,28 +159,17 @@ def test_pass_matches_previous_formulation(host):
 # ---- the wave-wide tail solver (csrc/plane_wide.h) over an emulated wave
 
 @pytest.fixture(scope="module")
-def wide(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("wide")), "libwide_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", *HOST_FLAGS, "-o", out,
-                           os.path.join(NATIVE, "wide_host.cpp")])
-    lib = ctypes.CDLL(out)
-    lib.wide_solve_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p]
-    lib.wide_check_fixpoint.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32]
-    lib.wide_check_fixpoint.restype = ctypes.c_int64
-    lib.wide_set_mrv_after.argtypes = [ctypes.c_uint32]
-    lib.wide_set_mrv_after(0)
-    return lib
+def wide():
+    return host_lib("wide_host")
 
 
-def _wide(lib, boards, node_order=0, lane_guesses=0, max_depth=81, stats=None):
+def _wide(lib, boards, node_order=0, lane_guesses=0, max_depth=81, mrv_after=0, stats=None):
     boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
     out = np.zeros_like(boards)
     st = np.zeros(len(boards), dtype=np.int32)
     g, pl, pw = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
     lib.wide_solve_batch(boards.ctypes.data, out.ctypes.data, st.ctypes.data, len(boards), node_order,
-                         max_depth, lane_guesses, ctypes.byref(g), ctypes.byref(pl), ctypes.byref(pw))
+                         max_depth, mrv_after, lane_guesses, ctypes.byref(g), ctypes.byref(pl), ctypes.byref(pw))
     if stats is not None:
         stats.update(guesses=g.value, passes_lane=pl.value, passes_wide=pw.value)
     return out, st
@@ -238,12 +207,9 @@ def test_wide_continuation_vs_lane_solver(host, wide, order, lane_guesses, mrv_a
     boards = _mixed_boards()
     no = int(order == "node")
     s_lane, s_wide = {}, {}
-    want, wst = _solve(host, boards, node_order=no, stats=s_lane)
-    wide.wide_set_mrv_after(mrv_after)  # the board's search mode is handed over too
-    try:
-        got, gst = _wide(wide, boards, node_order=no, lane_guesses=lane_guesses, stats=s_wide)
-    finally:
-        wide.wide_set_mrv_after(0)
+    want, wst = _solve(host, boards, node_order=no, mrv_after=mrv_after, stats=s_lane)
+    # (the board's search mode is handed over too)
+    got, gst = _wide(wide, boards, node_order=no, lane_guesses=lane_guesses, mrv_after=mrv_after, stats=s_wide)
     assert np.array_equal(gst, wst)
     assert np.array_equal(got, want)
     # (the completion count walks whole subtrees, contradictory states
@@ -275,7 +241,7 @@ def test_wide_edge_cases(wide):
 # ---- other pass variants
 
 @pytest.mark.parametrize("flags,group", [(0, 1), (1, 1), (5, 1), (7, 1), (3, 2), (3, 3), (3, 9), (7, 2)])
-def test_pass_variants_match_their_restatement(tmp_path, flags, group):
+def test_pass_variants_match_their_restatement(flags, group):
     """Every SDK_PLANE_LC rule-D variant (0 none, 1 box -> column, 2 box ->
     row -- 3, both, is the default, covered above --, 4 column -> box) and every
     SDK_PLANE_GROUP grouping of rule C's hidden singles (1 Gauss-Seidel, the
@@ -283,36 +249,20 @@ def test_pass_variants_match_their_restatement(tmp_path, flags, group):
     plain-loop restatement (plane_host.cpp v1::pass) after every pass, and
     the wave-wide pass reaches its fixpoints (wide_host.cpp), so a build with
     other flags stays exact."""
-    defines = ["-DSDK_PLANE_LC=%d" % flags, "-DSDK_PLANE_GROUP=%d" % group]
-    libs = {}
-    for name in ("plane_host", "wide_host"):
-        out = str(tmp_path / ("lib%s_%d_%d.so" % (name, flags, group)))
-        subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", *defines, "-o", out,
-                               os.path.join(NATIVE, name + ".cpp")])
-        libs[name] = ctypes.CDLL(out)
+    defines = ("SDK_PLANE_LC=%d" % flags, "SDK_PLANE_GROUP=%d" % group)
+    libs = {name: host_lib(name, defines) for name in ("plane_host", "wide_host")}
     from sudoku_solver_distributed_amd.gen import hard17_batch, hard_search_batch
     boards = np.ascontiguousarray(np.concatenate([hard17_batch(150, seed=21).numpy(),
                                                   hard_search_batch(150, seed=22).numpy()]))
-    chk = libs["plane_host"].plane_check_pass
-    chk.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64]
-    chk.restype = ctypes.c_int64
-    assert chk(boards.ctypes.data, len(boards), 50_000, 5) == 0
-    f = libs["wide_host"].wide_check_fixpoint
-    f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32]
-    f.restype = ctypes.c_int64
-    assert f(boards[:100].ctypes.data, 100, 5, 3) == 0
+    assert libs["plane_host"].plane_check_pass(boards.ctypes.data, len(boards), 50_000, 5) == 0
+    assert libs["wide_host"].wide_check_fixpoint(boards[:100].ctypes.data, 100, 5, 3) == 0
     if group > 1:  # and the solver's answers are the oracle's
-        lib = libs["plane_host"]
-        lib.plane_solve_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                          ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-        lib.plane_set_mrv_after.argtypes = [ctypes.c_uint32]
-        lib.plane_set_mrv_after(64)
-        sols, st = _solve(lib, boards)
+        sols, st = _solve(libs["plane_host"], boards, mrv_after=64)
         want, cnt = O.solve_unique_batch(boards)
         assert (cnt == 1).all() and (st == 1).all() and np.array_equal(sols, want)
 
 
-def test_open_root_rule_same_answers_fewer_passes(tmp_path):
+def test_open_root_rule_same_answers_fewer_passes():
     """SDK_PLANE_ROOT_OPEN (plane_solver.h): a board whose propagated root
     keeps >= 58 open cells counts its completions from the root at once.
     Same answers and statuses as without the rule (the count's one
@@ -322,18 +272,11 @@ def test_open_root_rule_same_answers_fewer_passes(tmp_path):
                                                   hard_search_batch(300, seed=32).numpy()]))
     res = {}
     for t in (0, 58):
-        out = str(tmp_path / ("libplane_root%d.so" % t))
-        subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-std=c++17", "-DSDK_PLANE_ROOT_OPEN=%d" % t,
-                               "-o", out, os.path.join(NATIVE, "plane_host.cpp")])
-        lib = ctypes.CDLL(out)
-        lib.plane_solve_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                          ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-        lib.plane_set_mrv_after.argtypes = [ctypes.c_uint32]
-        lib.plane_set_mrv_after(64)
+        lib = host_lib("plane_host", ("SDK_PLANE_ROOT_OPEN=%d" % t,))
         stats = {}
-        sols, st = _solve(lib, boards, stats=stats)
+        sols, st = _solve(lib, boards, mrv_after=64, stats=stats)
         hard = {}
-        _solve(lib, boards[:1500], stats=hard)
+        _solve(lib, boards[:1500], mrv_after=64, stats=hard)
         res[t] = (sols, st, hard["passes"])
     assert np.array_equal(res[0][0], res[58][0]) and np.array_equal(res[0][1], res[58][1])
     assert res[58][2] < 0.95 * res[0][2], (res[0][2], res[58][2])
