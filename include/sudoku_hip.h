@@ -9,6 +9,18 @@
  * Grid format: 81 bytes per board, row-major, 0 = empty, 1..9 = digit; a batch
  * of n boards is n*81 contiguous bytes.
  *
+ * Caller memory: a uint8_t array may start at any address (no alignment is
+ * asked of it); int32_t / int64_t arrays need their natural alignment (4 / 8
+ * bytes), a workspace, a scratch and a node state record 16 bytes.  No byte
+ * outside the documented extent of an output, scratch or workspace argument
+ * is ever written, and an input array is never modified, unless the caller
+ * passes it as an output too where that is allowed.  Aliasing an input with
+ * an output is allowed only where an entry says so (sdk_solve_batch,
+ * sdk_solve_batch_grid, sdk_solve_batches); every other entry needs its
+ * arguments disjoint.  (sdk_count_solutions_batch reads the aligned dwords
+ * that hold a board, so up to 3 bytes on either side of d_puzzles are read;
+ * they never change an answer.)
+ *
  * Return codes: 0 = launched / ok, <0 = error (text in sdk_last_error()).
  *
  * Each entry point replaces one reference interface
@@ -56,7 +68,8 @@ size_t sdk_workspace_bytes(void);
  *                  is_valid_move's short-circuit (node.py:44-45: every unit
  *                  sums to 45 -> any digit is accepted; only boards with
  *                  clashing givens can reach it).
- * d_puzzles and d_solutions may alias.
+ * d_puzzles and d_solutions may alias (the same pointer: an in-place solve;
+ * partly overlapping arrays are not allowed).
  * `ordered` != 0 selects frontier mode: once board i is solved, boards j > i
  * are abandoned (status SDK_CANCELLED) and the lowest solved index is kept in
  * the workspace (sdk_read_stats out[4]). */
@@ -90,7 +103,8 @@ int sdk_solve_batch_grid(const uint8_t *d_puzzles, uint8_t *d_solutions, int32_t
  * once per batch: a multi-step persistent launch (bench.py's strong-scaling
  * steps, where one GPU's share of a step is too small to fill the chip).
  * 1 <= count <= SDK_MAX_BATCHES; a batch may be empty; batches must not
- * overlap each other's outputs.  Returns 0 / -1 (HIP error) / -2 (bad
+ * overlap each other's outputs.  A batch may be solved in place
+ * (d_solutions[i] == d_puzzles[i]), as with sdk_solve_batch.  Returns 0 / -1 (HIP error) / -2 (bad
  * arguments).  Replaces the same reference walks as sdk_solve_batch
  * (gen.py:6-28, node.py:62-74), once per board. */
 #define SDK_MAX_BATCHES 32
@@ -99,7 +113,8 @@ int sdk_solve_batches(const uint8_t *const *d_puzzles, uint8_t *const *d_solutio
 
 /* Batch Sudoku.check (mode 0, sudoku.py:119-140: every row, column and box
  * sums to 45 and holds 9 distinct values) or node.py's SudokuSolver.check
- * (mode 1, node.py:82-116: sums only).  d_ok[i] = 1/0. */
+ * (mode 1, node.py:82-116: sums only).  d_ok[i] = 1/0.  d_ok must not alias
+ * d_grids. */
 int sdk_check_batch(const uint8_t *d_grids, int32_t *d_ok, int64_t n, int mode, void *stream);
 
 /* Batch of node.py "solve" tasks (node.py:384-406 -> 76-80,
@@ -118,7 +133,9 @@ int sdk_first_candidate_batch(const uint8_t *d_grids, const int32_t *d_cells,
  * failed), SDK_NO_RETURN (node.py loops forever on this board; d_out = the
  * board at that point) or SDK_INVALID (a byte > 9); d_validations[i] =
  * node.py's `validations` counter after the call (one per
- * SudokuSolver.check: every is_valid_move plus the final check). */
+ * SudokuSolver.check: every is_valid_move plus the final check).
+ * No two of the arrays may alias (d_out != d_boards), here and in
+ * sdk_peer_solve_seq. */
 int sdk_peer_solve_batch(const uint8_t *d_boards, uint8_t *d_out, int32_t *d_status, int32_t *d_validations,
                          int64_t n, void *stream);
 

@@ -436,8 +436,9 @@ __device__ __forceinline__ int psearch(PackLds &W, int lane, PCells &s, int64_t 
 }
 
 // One board (index p) by the whole wave: load, search, store, status.
-__device__ __forceinline__ void psolve_board(PackLds &W, int lane, PCells &s, const uint8_t *__restrict__ puzzles,
-                                             uint8_t *__restrict__ sols, int32_t *__restrict__ status, int64_t p,
+// puzzles and sols may be the same array (an in-place solve): no __restrict__
+__device__ __forceinline__ void psolve_board(PackLds &W, int lane, PCells &s, const uint8_t *puzzles,
+                                             uint8_t *sols, int32_t *__restrict__ status, int64_t p,
                                              unsigned long long *__restrict__ ws, const int64_t *best, int order,
                                              uint32_t &solved, uint32_t &guesses, uint32_t &sweeps)
 {

@@ -101,8 +101,9 @@ __device__ __forceinline__ int plane_slot_cell(int lane, int slot)
     return 27 * band + 9 * (pos / 10) + pos % 10;
 }
 
-// copy board q's 81 bytes from src to dst (lanes l and 64 + l)
-__device__ __forceinline__ void plane_copy_board(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int lane)
+// copy board q's 81 bytes from src to dst (lanes l and 64 + l); src == dst
+// for an in-place solve
+__device__ __forceinline__ void plane_copy_board(const uint8_t *src, uint8_t *dst, int lane)
 {
     dst[lane] = src[lane];
     if (lane < 17) dst[64 + lane] = src[64 + lane];

@@ -103,9 +103,10 @@ __global__ __launch_bounds__(BLOCK_THREADS, SDK_PACKED_WAVES_PER_EU) void solvep
 // Second pass behind the plane kernel: solve exactly the boards it left
 // (status SDK_DEFERRED): the deferred list's entries, one board per wave,
 // grid-stride; if the list overflowed, every wave scans 64 statuses per load
-// instead and runs the deferred ones among them.
+// instead and runs the deferred ones among them.  puzzles and sols may be the
+// same array (an in-place solve).
 __global__ __launch_bounds__(BLOCK_THREADS, SDK_PACKED_WAVES_PER_EU) void solvep_deferred_kernel(
-    const uint8_t *__restrict__ puzzles, uint8_t *__restrict__ sols, int32_t *__restrict__ status,
+    const uint8_t *puzzles, uint8_t *sols, int32_t *__restrict__ status,
     int64_t n, unsigned long long *__restrict__ ws, const int64_t *__restrict__ list, int ordered, int order)
 {
     __shared__ PackLds lds[WAVES_PER_BLOCK];
