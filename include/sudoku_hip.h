@@ -316,6 +316,57 @@ int sdk_canonical_batch(const uint8_t *d_boards, uint8_t *d_canon, int32_t *d_sy
                         int64_t n, int slices /* 0 = auto */, void *d_scratch, size_t scratch_bytes,
                         void *stream);
 
+/* Rate n puzzles: how much logic each one needs (library extension, no
+ * reference counterpart).  A board is 81 bytes 0..9.  Its state is a set of
+ * candidates per cell -- a given v starts as {v}, an empty cell as {1..9} --
+ * and the rules only remove candidates:
+ *   N  a cell with the one candidate d removes d from its 20 peers;
+ *   H  a digit with exactly one place in a row, column or box becomes that
+ *      cell's only candidate;
+ *   L  locked candidates: where a box and a row or column meet in three
+ *      cells that hold a place of d, and d has no other place in the box
+ *      (the line), d leaves the rest of the line (the box);
+ *   T  for a cell with two or more candidates and one of them, d: if the
+ *      {N, H, L} closure of the state with that cell fixed to d is dead, d
+ *      leaves the cell (one level of trial, never nested).
+ * A state is dead when a cell has no candidate or a unit has no place for a
+ * digit; solved when every cell has one candidate and it is not dead.  Level
+ * 1 is {N}, 2 {N, H}, 3 {N, H, L}, 4 {N, H, L, T}; closure_L is the level's
+ * rules applied until nothing changes.  The rules are monotone, so closure_L
+ * does not depend on the order they fire in.  For
+ * 1 <= max_level <= SDK_RATE_MAX_LEVEL:
+ *   d_rating[i]       = the lowest L <= max_level with closure_L solved; else
+ *                       0 when closure_max_level is dead (no completion
+ *                       exists: the rules are sound); else max_level + 1;
+ *   d_open[4 i + L-1] = the cells of closure_L without exactly one candidate;
+ *                       0 from the solving level on, -1 where closure_L is
+ *                       dead, SDK_RATE_NOT_RUN for L > max_level;
+ *   d_marks[81 i + c] = the candidates of cell c, bit d-1 for digit d, in the
+ *                       deepest closure computed (closure_rating when solved:
+ *                       the completion; else closure_max_level); all zero
+ *                       when that closure is dead.
+ * Givens that repeat a digit in a unit have rating 0 (N empties both cells).
+ * A byte > 9 gives SDK_INVALID in d_rating[i] and all four d_open entries,
+ * and zero marks.  d_open and d_marks may be NULL; d_marks needs 2-byte
+ * alignment, d_boards none.  Inputs are never modified and no byte outside
+ * these extents is written.
+ * d_scratch: at least sdk_rate_scratch_bytes(n, max_level) bytes of device
+ * memory, 8-byte aligned, contents irrelevant: the call re-arms its counters
+ * itself on `stream` (256 bytes, and at max_level 4 eight bytes per board:
+ * the list of the boards level 3 leaves open).  SINGLE-STREAM like a
+ * workspace; the solve workspace is not involved.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * max_level out of range, n negative or above 2^31 - 1, a NULL pointer that
+ * is required, a misaligned pointer, scratch too small), by return code only;
+ * arguments are checked before any launch and n == 0 returns 0.
+ * sdk_rate_scratch_bytes returns 0 for bad arguments. */
+#define SDK_RATE_MAX_LEVEL 4
+#define SDK_RATE_NOT_RUN -2
+size_t sdk_rate_scratch_bytes(int64_t n, int max_level);
+int sdk_rate_batch(const uint8_t *d_boards, int32_t *d_rating, int32_t *d_open /* n*4, NULL ok */,
+                   uint16_t *d_marks /* n*81, NULL ok */, int64_t n, int max_level, void *d_scratch,
+                   size_t scratch_bytes, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -48,12 +48,16 @@ EXPORTS = (
     "sdk_count_solutions_batch",
     "sdk_canonical_scratch_bytes",
     "sdk_canonical_batch",
+    "sdk_rate_scratch_bytes",
+    "sdk_rate_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
 SDK_COUNT_MAX_LIMIT = 1024  # sdk_count_solutions_batch: the largest cap
 SDK_CANON_SYMMETRIES = 3359232  # sdk_canonical_batch: 2 * 1296 * 1296
 SDK_CANON_MAX_SLICES = 2592  # ... and the most parts a board's search is cut into
+SDK_RATE_MAX_LEVEL = 4  # sdk_rate_batch: the deepest rule level (trial eliminations)
+SDK_RATE_NOT_RUN = -2  # ... and the open count of a level above max_level
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -121,6 +125,10 @@ def load() -> ctypes.CDLL:
     L.sdk_canonical_scratch_bytes.argtypes = [i64, i32]
     L.sdk_canonical_batch.restype = i32
     L.sdk_canonical_batch.argtypes = [vp, vp, vp, vp, i64, i32, vp, sz, vp]
+    L.sdk_rate_scratch_bytes.restype = sz
+    L.sdk_rate_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_rate_batch.restype = i32
+    L.sdk_rate_batch.argtypes = [vp, vp, vp, vp, i64, i32, vp, sz, vp]
     _lib = L
     return L
 

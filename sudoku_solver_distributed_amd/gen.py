@@ -179,6 +179,22 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
     return (puzzle, full) if return_solutions else puzzle
 
 
+def rated_batch(n: int, seed: Optional[int] = None, ratings=None, device=None, return_solutions: bool = False):
+    """unique_batch(n, seed=seed) with every puzzle's rating
+    (BatchSolver.rate, max_level 4: 1 naked singles .. 4 trial eliminations,
+    5 not decided by them; never 0, every puzzle has a completion):
+    (puzzles (k, 81) uint8, ratings (k,) int32[, full grids (k, 81)]), device
+    tensors.  ratings: keep only the puzzles whose rating is in this
+    collection, in the batch's order (k <= n); None keeps all n.  Library
+    extension, no reference counterpart."""
+    puzzles, full = unique_batch(n, seed=seed, device=device, return_solutions=True)
+    rating = get_solver(device).rate(puzzles)
+    if ratings is not None:
+        keep = torch.isin(rating, torch.as_tensor(sorted(int(r) for r in ratings), dtype=torch.int32, device=rating.device))
+        puzzles, full, rating = puzzles[keep], full[keep], rating[keep]
+    return (puzzles, rating, full) if return_solutions else (puzzles, rating)
+
+
 # ------------------------------------------------------------ symmetry classes
 _PERM3 = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
 CANON_SYMMETRIES = 2 * 1296 * 1296

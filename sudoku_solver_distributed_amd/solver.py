@@ -131,6 +131,7 @@ class BatchSolver:
         self._pool_lock = threading.Lock()  # builds _pool / _slots once across threads
         self._count_scratch = None  # count_solutions' scratch, grown on demand (under self._lock)
         self._canon_scratch = None  # canonical's scratch, likewise
+        self._rate_scratch = None  # rate's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -265,6 +266,42 @@ class BatchSolver:
         self._rc_only(rc, "sdk_canonical_batch")
         out = (canon,) + ((sym,) if return_sym else ()) + ((autos,) if return_autos else ())
         return out if len(out) > 1 else canon
+
+    # --------------------------------------------------------------- rate
+    def rate(self, boards, max_level: int = 4, return_open: bool = False, return_marks: bool = False, stream=None):
+        """How much logic every puzzle needs, as an int32 (n,) tensor
+        (sdk_rate_batch; library extension, no reference counterpart; the
+        definition is in include/sudoku_hip.h and DESIGN.md §14): the lowest
+        level whose rules solve the board -- 1 naked singles, 2 with hidden
+        singles, 3 with locked candidates, 4 with one level of trial
+        eliminations -- 0 when the rules prove that it has no completion,
+        max_level + 1 when max_level does not decide it.  The rating does not
+        depend on any search order and is the same for every symmetry image
+        of a board.  return_open: also an int32 (n, 4) tensor, per level the
+        cells left without exactly one candidate (0 from the solving level
+        on, -1 where the level's closure is dead, SDK_RATE_NOT_RUN (-2) above
+        max_level); return_marks: also an int16 (n, 81) tensor, per cell the
+        candidates the deepest closure computed leaves (bit d-1 for digit d;
+        the completion as single bits when solved, zero when dead).  A byte
+        > 9 gives SDK_INVALID (-1) in the rating and the open counts.
+        Asynchronous on the stream; one cached scratch tensor serves every
+        call, ordered like the workspace's."""
+        max_level = int(max_level)
+        if not 1 <= max_level <= _lib.SDK_RATE_MAX_LEVEL:
+            raise ValueError(f"max_level must be 1..{_lib.SDK_RATE_MAX_LEVEL}")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        rating = torch.empty(n, dtype=torch.int32, device=self.device)
+        opens = torch.empty((n, 4), dtype=torch.int32, device=self.device) if return_open else None
+        marks = torch.empty((n, 81), dtype=torch.int16, device=self.device) if return_marks else None
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_rate_scratch", int(self.lib.sdk_rate_scratch_bytes(n, max_level)))
+            rc = self.lib.sdk_rate_batch(p.data_ptr(), rating.data_ptr(), opens.data_ptr() if return_open else None,
+                                         marks.data_ptr() if return_marks else None, n, max_level,
+                                         sc.data_ptr(), sc.numel(), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_rate_batch")
+        out = (rating,) + ((opens,) if return_open else ()) + ((marks,) if return_marks else ())
+        return out if len(out) > 1 else rating
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
