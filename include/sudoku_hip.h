@@ -367,6 +367,46 @@ int sdk_rate_batch(const uint8_t *d_boards, int32_t *d_rating, int32_t *d_open /
                    uint16_t *d_marks /* n*81, NULL ok */, int64_t n, int max_level, void *d_scratch,
                    size_t scratch_bytes, void *stream);
 
+/* The exact candidates of n boards (library extension, no reference
+ * counterpart).  A completion of a board is a valid Sudoku grid -- every row,
+ * column and box holds 1..9 once -- that keeps the givens.
+ *   d_marks[81 i + c] = the digits that at least one completion of board i
+ *                       puts into cell c, bit d-1 for digit d (the format of
+ *                       sdk_rate_batch's marks): a given's own bit when the
+ *                       board has a completion, all zero when it has none;
+ *   d_count[i]        = min(2, completions): 0 for zero marks, 1 when every
+ *                       cell has one bit (the marks are the completion), 2
+ *                       otherwise.
+ * The answer is exact, with no cap and no truncated case: it does not depend
+ * on any search order and the marks of a symmetry image of a board are the
+ * image of its marks.  sdk_rate_batch's marks are a superset of these.  The
+ * work is one capped count and then at most one first-completion search per
+ * candidate still unwitnessed, not an enumeration.
+ * A board whose givens repeat a digit in a row, column or box has no
+ * completion: zero marks, count 0.  A byte > 9 gives zero marks and
+ * SDK_INVALID in d_count[i]; SDK_FAULT (with zero marks) would mean a search
+ * outgrew its stack, which 81 levels make impossible.
+ * d_count may be NULL.  d_marks needs 2-byte alignment (d_count 4), d_boards
+ * none.  Inputs are never modified, no byte outside these extents is written,
+ * and the arguments are disjoint.
+ * d_scratch: at least sdk_candidates_scratch_bytes(n, max_waves) bytes of
+ * device memory, 8-byte aligned, contents irrelevant: the call re-arms its
+ * queue head itself on `stream`.  SINGLE-STREAM like a workspace; the solve
+ * workspace, its counters and sdk_verify_workspace are not involved.
+ * max_waves caps the kernel's grid (0: as many waves as fit on the device at
+ * the kernel's occupancy); results never depend on it.  The scratch holds 256
+ * bytes and, per wave of min(ceil(n / 64), waves), 64 lanes x 83 lines x 128
+ * bytes (about 680 KB: little for a small call, about 2.8 GB for a full grid
+ * on an MI355X).
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * negative n or max_waves, a NULL pointer that is required, a misaligned
+ * pointer, scratch too small), by return code only (sdk_last_error() is not
+ * set); arguments are checked before any launch and n == 0 returns 0.
+ * sdk_candidates_scratch_bytes returns 0 for negative arguments. */
+size_t sdk_candidates_scratch_bytes(int64_t n, int max_waves);
+int sdk_candidates_batch(const uint8_t *d_boards, uint16_t *d_marks /* n*81 */, int32_t *d_count /* n, NULL ok */,
+                         int64_t n, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

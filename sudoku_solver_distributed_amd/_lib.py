@@ -50,6 +50,8 @@ EXPORTS = (
     "sdk_canonical_batch",
     "sdk_rate_scratch_bytes",
     "sdk_rate_batch",
+    "sdk_candidates_scratch_bytes",
+    "sdk_candidates_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -129,6 +131,10 @@ def load() -> ctypes.CDLL:
     L.sdk_rate_scratch_bytes.argtypes = [i64, i32]
     L.sdk_rate_batch.restype = i32
     L.sdk_rate_batch.argtypes = [vp, vp, vp, vp, i64, i32, vp, sz, vp]
+    L.sdk_candidates_scratch_bytes.restype = sz
+    L.sdk_candidates_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_candidates_batch.restype = i32
+    L.sdk_candidates_batch.argtypes = [vp, vp, vp, i64, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(_HERE)
 # iterative-minreg keeps its board loader from spilling: 116 VGPRs and no
 # scratch, where LLVM's default scheduler spills 34 registers, DESIGN.md §12;
 # canon_kernels.hip, the canonical form, and rate_kernels.hip, the puzzle
-# rating, likewise units of their own, LLVM's defaults)
+# rating, likewise units of their own, LLVM's defaults; cand_kernels.hip, the
+# exact candidates, a unit of its own with the count's scheduler)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -35,7 +36,8 @@ def sources(sched: str = _SCHED):
             ("plane_kernels.hip", ([] if sched == "default" else ["-mllvm", f"-amdgpu-sched-strategy={sched}"]) + extra),
             ("count_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("canon_kernels.hip", []),
-            ("rate_kernels.hip", []))
+            ("rate_kernels.hip", []),
+            ("cand_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
 
 
 SRCS = sources()

@@ -29,7 +29,7 @@ inline void words_of(const uint8_t *src, uint32_t (&x)[21])
 // cells (the look-ahead path only).  The put / get plane::WordStack wraps.
 // deepest: the most levels in use since the caller last zeroed it.
 struct LineStack {
-    enum { LEVELS = 82 };
+    enum { LEVELS = 83 };  // (the candidates' lanes: 81 levels, the root's line and the witnesses', plane_cand.h)
     uint32_t w[LEVELS * plane::STACK_LINE_WORDS];
     uint32_t deepest = 0;
     void put(uint32_t level, int k, uint32_t v)

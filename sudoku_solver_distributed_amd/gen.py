@@ -19,6 +19,9 @@
   one solution (minimal ones by default), certified removal by removal by the
   GPU's completion count (library extension; the reference's generate_sudoku
   erases cells blindly and its 55-empty boards are almost never unique).
+* ``make_unique(boards)`` -- boards with several completions repaired into
+  proper puzzles: givens added where the GPU's exact candidates
+  (BatchSolver.candidates; library extension) leave a cell open.
 * ``apply_symmetry(boards, sym)`` / ``class_ids(boards)`` -- the symmetry
   group in numbers and the isomorphism class of every board, by the GPU's
   canonical form (BatchSolver.canonical; library extension).
@@ -193,6 +196,42 @@ def rated_batch(n: int, seed: Optional[int] = None, ratings=None, device=None, r
         keep = torch.isin(rating, torch.as_tensor(sorted(int(r) for r in ratings), dtype=torch.int32, device=rating.device))
         puzzles, full, rating = puzzles[keep], full[keep], rating[keep]
     return (puzzles, rating, full) if return_solutions else (puzzles, rating)
+
+
+def make_unique(boards, device=None):
+    """Boards with several completions turned into proper puzzles by adding
+    givens: (puzzles (n, 81) uint8, added (n,) int32), device tensors.  Library
+    extension, no reference counterpart.
+
+    Each round takes marks = BatchSolver.candidates(board), the digits some
+    completion puts into each cell.  A board with a cell of two or more
+    candidates gets the cell with the MOST candidates (ties: the lowest
+    index) set to its LOWEST candidate; the loop ends when a round changes
+    nothing.  Every choice is a true candidate, so a board never loses its
+    last completion, and it ends with exactly one.  Boards with one
+    completion, with none, or with a byte > 9 come back unchanged (added 0).
+    The givens are kept; added[i] is the number of new ones."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(boards, max_value=255)).clone()
+    n = p.shape[0]
+    added = torch.zeros(n, dtype=torch.int32, device=p.device)
+    live = torch.arange(n, dtype=torch.int64, device=p.device)
+    bit = torch.arange(9, dtype=torch.int32, device=p.device)
+    rank = 80 - torch.arange(81, dtype=torch.int32, device=p.device)  # ties: the lowest index first
+    while live.numel():
+        marks = solver.candidates(p[live]).to(torch.int32)
+        width = ((marks.unsqueeze(2) >> bit) & 1).sum(2, dtype=torch.int32)  # candidates per cell
+        cell = (width * 128 + rank).argmax(1, keepdim=True)
+        still = width.gather(1, cell).squeeze(1) >= 2
+        live, cell = live[still], cell[still]
+        if not live.numel():
+            break
+        m = marks[still].gather(1, cell)
+        low = m & -m
+        digit = (((low - 1).unsqueeze(2) >> bit) & 1).sum(2) + 1  # the lowest candidate: 1 + its bit number
+        p[live, cell.squeeze(1)] = digit.squeeze(1).to(torch.uint8)
+        added[live] += 1
+    return p, added
 
 
 # ------------------------------------------------------------ symmetry classes

@@ -132,6 +132,7 @@ class BatchSolver:
         self._count_scratch = None  # count_solutions' scratch, grown on demand (under self._lock)
         self._canon_scratch = None  # canonical's scratch, likewise
         self._rate_scratch = None  # rate's scratch, likewise
+        self._cand_scratch = None  # candidates' scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -302,6 +303,37 @@ class BatchSolver:
         self._rc_only(rc, "sdk_rate_batch")
         out = (rating,) + ((opens,) if return_open else ()) + ((marks,) if return_marks else ())
         return out if len(out) > 1 else rating
+
+    # --------------------------------------------------------- candidates
+    def candidates(self, boards, return_count: bool = False, stream=None, max_waves: int = 0):
+        """The exact candidates of every board, as an int16 (n, 81) tensor
+        (sdk_candidates_batch; library extension, no reference counterpart;
+        DESIGN.md §15): bit d-1 of marks[i, c] is set exactly when at least
+        one completion of board i -- a valid Sudoku grid that keeps the givens
+        -- puts digit d into cell c (rate()'s marks format; those marks are a
+        superset of these).  A cell with one bit is forced (a given shows its
+        own bit), a cell with several is where the board stays open, and a
+        board with no completion has all marks zero.  There is no cap and no
+        truncated case; the answer depends on no search order and the marks
+        of a symmetry image of a board are the image of its marks.
+        return_count: also an int32 (n,) tensor, min(2, completions): 0 for
+        zero marks, 1 when every cell has one bit, 2 otherwise; SDK_INVALID
+        (-1, with zero marks) for a byte > 9.  Givens that repeat a digit in a
+        unit have no completion.  max_waves > 0 caps the kernel's grid;
+        results never depend on it.  Asynchronous on the stream; one cached
+        scratch tensor serves every call, ordered like the workspace's."""
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        marks = torch.empty((n, 81), dtype=torch.int16, device=self.device)
+        count = torch.empty(n, dtype=torch.int32, device=self.device) if return_count else None
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_cand_scratch", int(self.lib.sdk_candidates_scratch_bytes(n, int(max_waves))))
+            rc = self.lib.sdk_candidates_batch(p.data_ptr(), marks.data_ptr(), count.data_ptr() if return_count else None,
+                                               n, sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_candidates_batch")
+        return (marks, count) if return_count else marks
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
