@@ -407,6 +407,55 @@ size_t sdk_candidates_scratch_bytes(int64_t n, int max_waves);
 int sdk_candidates_batch(const uint8_t *d_boards, uint16_t *d_marks /* n*81 */, int32_t *d_count /* n, NULL ok */,
                          int64_t n, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
 
+/* Redundant givens of n boards: minimise a puzzle, or probe which of its
+ * clues it could lose (library extension, no reference counterpart).  A
+ * completion is what sdk_count_solutions_batch counts: a valid Sudoku grid
+ * that keeps the givens.
+ *   d_status[i] = min(2, completions of board i); clashing givens give 0, a
+ *                 byte > 9 SDK_INVALID; SDK_FAULT would mean a search outgrew
+ *                 its stack, which 81 levels make impossible, and gives
+ *                 out = input, never a partial result.
+ * For every status but 1, d_out row i is the input row and d_removed[i] = 0.
+ * Status 1, SDK_MIN_GREEDY: P starts as the board.  The turns run t = 0..80
+ * with c = d_order[81 i + t], or c = t when d_order is NULL.  A turn is
+ * skipped when c > 80 or P[c] == 0; the loop ends once P has max_empty or more
+ * zero cells (the input's own zeros count); otherwise P[c] is erased if P
+ * without it still has exactly one completion.  d_out row i = the final P,
+ * d_removed[i] = the givens erased.  With max_empty = 81 and an order that
+ * names every given the result is a minimal proper puzzle.  d_order needs no
+ * validation: repeats and bytes above 80 are harmless by the skip rule.
+ * 0 <= max_empty <= 81.
+ * Status 1, SDK_MIN_PROBE: d_order and max_empty are not read.  Every given
+ * is tested alone against the INPUT board; d_out row i = the board with every
+ * individually redundant given erased (the clues every proper sub-puzzle must
+ * keep; in general not a proper puzzle itself), d_removed[i] = how many were
+ * erased.  A puzzle is minimal exactly when d_removed[i] == 0.
+ * Each test is one first-completion search of the puzzle with the cell opened
+ * to every digit but its own, not a count.
+ * d_order and d_removed may be NULL.  d_out must not alias d_boards; all
+ * arguments are disjoint.  Byte arrays may start at any address, the int32
+ * arrays need 4-byte alignment.  Inputs are never modified and no byte outside
+ * these extents is written.
+ * d_scratch: at least sdk_minimize_scratch_bytes(n, max_waves) bytes of device
+ * memory, 8-byte aligned, contents irrelevant: the call re-arms its queue head
+ * itself on `stream`.  SINGLE-STREAM like a workspace; the solve workspace,
+ * its counters and sdk_verify_workspace are not involved.  max_waves caps the
+ * kernel's grid (0: as many waves as fit on the device at the kernel's
+ * occupancy); results never depend on it.  The scratch holds 256 bytes and,
+ * per wave of min(ceil(n / 64), waves), 64 lanes x 82 lines x 128 bytes.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * a mode or max_empty out of range, negative n or max_waves, a NULL pointer
+ * that is required, a misaligned pointer, scratch too small, d_out ==
+ * d_boards), by return code only (sdk_last_error() is not set); arguments are
+ * checked before any launch and n == 0 returns 0 before any other check.
+ * sdk_minimize_scratch_bytes returns 0 for negative arguments. */
+#define SDK_MIN_GREEDY 0
+#define SDK_MIN_PROBE 1
+size_t sdk_minimize_scratch_bytes(int64_t n, int max_waves);
+int sdk_minimize_batch(const uint8_t *d_boards, const uint8_t *d_order /* n*81, NULL ok */, uint8_t *d_out /* n*81 */,
+                       int32_t *d_status /* n */, int32_t *d_removed /* n, NULL ok */, int64_t n, int mode,
+                       int max_empty, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -52,6 +52,8 @@ EXPORTS = (
     "sdk_rate_batch",
     "sdk_candidates_scratch_bytes",
     "sdk_candidates_batch",
+    "sdk_minimize_scratch_bytes",
+    "sdk_minimize_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -60,6 +62,8 @@ SDK_CANON_SYMMETRIES = 3359232  # sdk_canonical_batch: 2 * 1296 * 1296
 SDK_CANON_MAX_SLICES = 2592  # ... and the most parts a board's search is cut into
 SDK_RATE_MAX_LEVEL = 4  # sdk_rate_batch: the deepest rule level (trial eliminations)
 SDK_RATE_NOT_RUN = -2  # ... and the open count of a level above max_level
+SDK_MIN_GREEDY = 0  # sdk_minimize_batch: erase givens turn by turn while one completion is left
+SDK_MIN_PROBE = 1   # ... or test every given alone against the input board
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -135,6 +139,10 @@ def load() -> ctypes.CDLL:
     L.sdk_candidates_scratch_bytes.argtypes = [i64, i32]
     L.sdk_candidates_batch.restype = i32
     L.sdk_candidates_batch.argtypes = [vp, vp, vp, i64, vp, sz, i32, vp]
+    L.sdk_minimize_scratch_bytes.restype = sz
+    L.sdk_minimize_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_minimize_batch.restype = i32
+    L.sdk_minimize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -17,8 +17,9 @@
   applied to 256 minimal puzzles that need real search (data/).
 * ``unique_batch(n, empty_boxes, seed)`` -- proper puzzles: boards with exactly
   one solution (minimal ones by default), certified removal by removal by the
-  GPU's completion count (library extension; the reference's generate_sudoku
-  erases cells blindly and its 55-empty boards are almost never unique).
+  GPU's completion count, or by one BatchSolver.minimize call with fused=True
+  (library extension; the reference's generate_sudoku erases cells blindly and
+  its 55-empty boards are almost never unique).
 * ``make_unique(boards)`` -- boards with several completions repaired into
   proper puzzles: givens added where the GPU's exact candidates
   (BatchSolver.candidates; library extension) leave a cell open.
@@ -141,7 +142,7 @@ def generate_batch(n: int, empty_boxes: int, seed: Optional[int] = None, device=
 
 
 def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, device=None,
-                 return_solutions: bool = False, distinct: bool = False):
+                 return_solutions: bool = False, distinct: bool = False, fused: bool = False):
     """n puzzles with exactly ONE solution, as a (n, 81) uint8 device tensor
     (and their full grids).  Library extension, no reference counterpart.
 
@@ -161,10 +162,25 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
     distinct=True keeps only the first puzzle of every isomorphism class
     (class_ids), in the batch's order, and the matching rows of the full
     grids: fewer than n boards when two puzzles are symmetry images of each
-    other."""
+    other.
+
+    fused=True: step 3's 81 rounds as ONE BatchSolver.minimize(full, order,
+    max_empty=empty_boxes) call (library extension): the same
+    full grids and orders, and bit for bit the same puzzles."""
     solver = get_solver(device)
     full = generate_batch(n, 0, seed, device=device)
     order = np.argsort(np.random.default_rng(seed).random((n, 81)), axis=1)
+    if fused:
+        puzzle = full.clone()
+        if n and empty_boxes > 0:
+            turns = torch.as_tensor(order.astype(np.uint8), device=full.device)
+            puzzle, status = solver.minimize(full, turns, max_empty=min(int(empty_boxes), 81))
+            if not bool((status == 1).all().item()):
+                raise RuntimeError("a full grid was not reported as its own one completion")
+        if distinct and n:
+            first = torch.sort(class_ids(puzzle, device=device)[2]).values
+            puzzle, full = puzzle[first], full[first]
+        return (puzzle, full) if return_solutions else puzzle
     order = torch.as_tensor(order, dtype=torch.int64, device=full.device)
     puzzle = full.clone()
     empties = torch.zeros(n, dtype=torch.int64, device=full.device)

@@ -133,6 +133,7 @@ class BatchSolver:
         self._canon_scratch = None  # canonical's scratch, likewise
         self._rate_scratch = None  # rate's scratch, likewise
         self._cand_scratch = None  # candidates' scratch, likewise
+        self._min_scratch = None  # minimize's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -334,6 +335,57 @@ class BatchSolver:
                                                n, sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
         self._rc_only(rc, "sdk_candidates_batch")
         return (marks, count) if return_count else marks
+
+    # ----------------------------------------------------------- minimize
+    def minimize(self, boards, order=None, max_empty: int = 81, probe: bool = False, return_removed: bool = False,
+                 stream=None, max_waves: int = 0):
+        """Redundant givens (sdk_minimize_batch; library extension, no
+        reference counterpart): (puzzles uint8 (n, 81), status
+        int32 (n,)), plus removed int32 (n,) with return_removed.  status[i] =
+        min(2, completions of board i): 0 also for givens that repeat a digit
+        in a unit, SDK_INVALID (-1) for a byte > 9.  Only a board with exactly
+        one completion is changed; every other row comes back as it is, with
+        removed 0.
+        Greedy (the default): the board's givens are erased turn by turn --
+        turn t takes cell order[i, t] (an (n, 81) tensor of cell numbers; a
+        value above 80, a repeat or an empty cell skips the turn), or cell t
+        when order is None -- while the puzzle keeps its one completion, until
+        it has max_empty (0..81) empty cells, the input's own included.  With
+        max_empty=81 and an order that names every given the result is a
+        minimal proper puzzle.
+        probe=True: order and max_empty are not read; every given is tested
+        alone against the input board and the row returned has every
+        individually redundant given erased (in general not a proper puzzle);
+        a puzzle is minimal exactly when removed is 0.
+        max_waves > 0 caps the kernel's grid; results never depend on it.
+        Asynchronous on the stream; one cached scratch tensor serves every
+        call, ordered like the workspace's."""
+        max_empty = int(max_empty)
+        if not 0 <= max_empty <= 81:
+            raise ValueError("max_empty must be 0..81")
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        if order is not None:
+            order = torch.as_tensor(order)
+            if tuple(order.shape) != (n, 81):
+                raise ValueError("order must have shape (n, 81)")
+            if order.dtype != torch.uint8:  # a number that is no cell skips its turn
+                order = torch.where((order < 0) | (order > 80), 255, order).to(torch.uint8)
+            order = self._dev(order)
+        out = torch.empty_like(p)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        removed = torch.empty(n, dtype=torch.int32, device=self.device) if return_removed else None
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_min_scratch", int(self.lib.sdk_minimize_scratch_bytes(n, int(max_waves))))
+            rc = self.lib.sdk_minimize_batch(p.data_ptr(), order.data_ptr() if order is not None else None,
+                                             out.data_ptr(), status.data_ptr(),
+                                             removed.data_ptr() if return_removed else None, n,
+                                             _lib.SDK_MIN_PROBE if probe else _lib.SDK_MIN_GREEDY, max_empty,
+                                             sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_minimize_batch")
+        return (out, status, removed) if return_removed else (out, status)
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
