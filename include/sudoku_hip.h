@@ -456,6 +456,71 @@ int sdk_minimize_batch(const uint8_t *d_boards, const uint8_t *d_order /* n*81, 
                        int32_t *d_status /* n */, int32_t *d_removed /* n, NULL ok */, int64_t n, int mode,
                        int max_empty, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
 
+/* A random completion of every item: random full grids, random grids that
+ * contain a pattern of givens, another solution of an ambiguous board (library
+ * extension, no reference counterpart).  A completion is what
+ * sdk_count_solutions_batch counts: a valid Sudoku grid that keeps the givens.
+ * Items: items = n * per_board, 1 <= per_board, items <= 2^31 - 1.  Item q
+ * samples board q / per_board under key = first_key + q (mod 2^64) and writes
+ * row q of d_out and d_status[q].  An item's answer is a function of its
+ * board's 81 bytes, seed and key alone: not of max_waves, of the batch it came
+ * in or of its place in it, so a batch may be cut anywhere and continued with
+ * first_key moved on.
+ *   d_status[q] = 1  a completion was found: row q is a valid grid that keeps
+ *                    the givens
+ *                 0  the board has none (givens that repeat a digit in a unit
+ *                    included): row q is the input board
+ *                 SDK_INVALID  a byte > 9: row q is the input board
+ *                 SDK_FAULT    the search outgrew its stack, which 81 levels
+ *                    make impossible: row q is the input board, never a
+ *                    partial grid
+ * d_boards == NULL: every board is empty, no board byte is read, and the
+ * status is always 1 (random full grids).
+ * The rule, so that a caller can restate it.  The search is the count's: the
+ * library's propagation to a fixpoint; there, a branch on a fewest-candidates
+ * cell (the cell choice is deterministic); at a contradiction, back to the
+ * deepest branch that has a digit left; the first completion met is the
+ * answer.  Only the digit of a branch is random -- out of the cell's
+ * candidates on a new branch, out of the branch's remaining digits on a
+ * return to it.  With all arithmetic mod 2^64 and `mask` the digits to choose
+ * from (bit d-1 for digit d):
+ *     mix(x):   x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;
+ *               x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     h       = mix(mix(seed) + key)
+ *     r_t     = mix(h + (t + 1) * 0x9E3779B97F4A7C15)
+ *                   t = 0, 1, 2, ... counts this item's choices so far; every
+ *                   choice advances t, also when the mask has one bit
+ *     index   = ((r_t >> 32) * popcount(mask)) >> 32
+ *     digit   = the index-th lowest set bit of mask
+ * What this is and what it is not.  Each branch picks uniformly among the
+ * digits left in the cell.  Every completion of the board has positive
+ * probability: choosing a completion's own digit at every branch never dies,
+ * because the rules only remove digits that no completion uses.  The
+ * distribution over completions is that of a randomised search; it is NOT
+ * uniform.  The search is complete: status 0 is a proof that there is none.
+ * d_out must not alias d_boards; all arguments are disjoint.  d_boards and
+ * d_out may start at any address, d_status needs 4-byte alignment.  Inputs are
+ * never modified and no byte outside these extents is written.
+ * d_scratch: at least sdk_sample_scratch_bytes(items, max_waves) bytes of
+ * device memory, 8-byte aligned, contents irrelevant: the call re-arms its
+ * queue head itself on `stream`.  SINGLE-STREAM like a workspace; the solve
+ * workspace, its counters and sdk_verify_workspace are not involved.
+ * max_waves caps the kernel's grid (0: as many waves as fit on the device at
+ * the kernel's occupancy); results never depend on it.  The scratch holds 256
+ * bytes and, per wave of min(ceil(items / 64), waves), 64 lanes x 81 lines x
+ * 128 bytes.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * negative n or max_waves, per_board < 1, more than 2^31 - 1 items, a NULL
+ * d_out, d_status or d_scratch, a misaligned d_status or d_scratch, d_out ==
+ * d_boards, scratch too small), by return code only (sdk_last_error() is not
+ * set); arguments are checked before any launch and n == 0 returns 0 before
+ * any other check.  sdk_sample_scratch_bytes returns 0 for negative
+ * arguments. */
+size_t sdk_sample_scratch_bytes(int64_t items, int max_waves);
+int sdk_sample_batch(const uint8_t *d_boards /* n*81, NULL = every board empty */, uint8_t *d_out /* items*81 */,
+                     int32_t *d_status /* items */, int64_t n, int per_board, uint64_t seed, uint64_t first_key,
+                     void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -54,6 +54,8 @@ EXPORTS = (
     "sdk_candidates_batch",
     "sdk_minimize_scratch_bytes",
     "sdk_minimize_batch",
+    "sdk_sample_scratch_bytes",
+    "sdk_sample_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -143,6 +145,10 @@ def load() -> ctypes.CDLL:
     L.sdk_minimize_scratch_bytes.argtypes = [i64, i32]
     L.sdk_minimize_batch.restype = i32
     L.sdk_minimize_batch.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, i32, vp]
+    L.sdk_sample_scratch_bytes.restype = sz
+    L.sdk_sample_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_sample_batch.restype = i32
+    L.sdk_sample_batch.argtypes = [vp, vp, vp, i64, i32, ctypes.c_uint64, ctypes.c_uint64, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -20,6 +20,9 @@
   GPU's completion count, or by one BatchSolver.minimize call with fused=True
   (library extension; the reference's generate_sudoku erases cells blindly and
   its 55-empty boards are almost never unique).
+* ``random_grids(n, seed)`` -- n random full grids from the GPU's seeded
+  randomised search (BatchSolver.random_grids; library extension), with no
+  host loop; ``unique_batch(..., grids="random")`` builds its puzzles on them.
 * ``make_unique(boards)`` -- boards with several completions repaired into
   proper puzzles: givens added where the GPU's exact candidates
   (BatchSolver.candidates; library extension) leave a cell open.
@@ -141,8 +144,27 @@ def generate_batch(n: int, empty_boxes: int, seed: Optional[int] = None, device=
     return (puzzles, full) if return_solutions else puzzles
 
 
+def random_grids(n: int, seed: Optional[int] = None, device=None) -> torch.Tensor:
+    """n random full grids as a (n, 81) uint8 device tensor: the GPU's seeded
+    randomised search on the empty board (BatchSolver.random_grids, keys
+    0..n-1; library extension, no reference counterpart -- the reference's
+    generate_sudoku is still generate_batch).  Every valid grid can come out;
+    they are not equally likely.  seed=None draws a seed from `random`."""
+    if seed is None:
+        seed = _random.getrandbits(64)
+    return get_solver(device).random_grids(n, seed)
+
+
+def _full_grids(n: int, seed: Optional[int], device, grids: str) -> torch.Tensor:
+    if grids == "walk":
+        return generate_batch(n, 0, seed, device=device)
+    if grids == "random":
+        return random_grids(n, seed, device=device)
+    raise ValueError('grids must be "walk" or "random"')
+
+
 def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, device=None,
-                 return_solutions: bool = False, distinct: bool = False, fused: bool = False):
+                 return_solutions: bool = False, distinct: bool = False, fused: bool = False, grids: str = "walk"):
     """n puzzles with exactly ONE solution, as a (n, 81) uint8 device tensor
     (and their full grids).  Library extension, no reference counterpart.
 
@@ -166,9 +188,13 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
 
     fused=True: step 3's 81 rounds as ONE BatchSolver.minimize(full, order,
     max_empty=empty_boxes) call (library extension): the same
-    full grids and orders, and bit for bit the same puzzles."""
+    full grids and orders, and bit for bit the same puzzles.
+
+    grids="random": step 1 takes full = random_grids(n, seed) instead, random
+    full grids made on the GPU without a host loop; every
+    later step is the same.  "walk" is generate_batch's grids, as before."""
     solver = get_solver(device)
-    full = generate_batch(n, 0, seed, device=device)
+    full = _full_grids(n, seed, device, grids)
     order = np.argsort(np.random.default_rng(seed).random((n, 81)), axis=1)
     if fused:
         puzzle = full.clone()
@@ -198,15 +224,16 @@ def unique_batch(n: int, empty_boxes: int = 81, seed: Optional[int] = None, devi
     return (puzzle, full) if return_solutions else puzzle
 
 
-def rated_batch(n: int, seed: Optional[int] = None, ratings=None, device=None, return_solutions: bool = False):
+def rated_batch(n: int, seed: Optional[int] = None, ratings=None, device=None, return_solutions: bool = False,
+                grids: str = "walk"):
     """unique_batch(n, seed=seed) with every puzzle's rating
     (BatchSolver.rate, max_level 4: 1 naked singles .. 4 trial eliminations,
     5 not decided by them; never 0, every puzzle has a completion):
     (puzzles (k, 81) uint8, ratings (k,) int32[, full grids (k, 81)]), device
     tensors.  ratings: keep only the puzzles whose rating is in this
-    collection, in the batch's order (k <= n); None keeps all n.  Library
-    extension, no reference counterpart."""
-    puzzles, full = unique_batch(n, seed=seed, device=device, return_solutions=True)
+    collection, in the batch's order (k <= n); None keeps all n.  grids:
+    unique_batch's.  Library extension, no reference counterpart."""
+    puzzles, full = unique_batch(n, seed=seed, device=device, return_solutions=True, grids=grids)
     rating = get_solver(device).rate(puzzles)
     if ratings is not None:
         keep = torch.isin(rating, torch.as_tensor(sorted(int(r) for r in ratings), dtype=torch.int32, device=rating.device))

@@ -134,6 +134,7 @@ class BatchSolver:
         self._rate_scratch = None  # rate's scratch, likewise
         self._cand_scratch = None  # candidates' scratch, likewise
         self._min_scratch = None  # minimize's scratch, likewise
+        self._sample_scratch = None  # sample's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -386,6 +387,62 @@ class BatchSolver:
                                              sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
         self._rc_only(rc, "sdk_minimize_batch")
         return (out, status, removed) if return_removed else (out, status)
+
+    # ------------------------------------------------------------- sample
+    def sample(self, boards, seed: int = 0, per_board: int = 1, first_key: int = 0, stream=None, max_waves: int = 0):
+        """A random completion of every item (sdk_sample_batch; library
+        extension, no reference counterpart): (grids uint8
+        (n * per_board, 81), status int32 (n * per_board,)).  Item q samples
+        board q // per_board under key first_key + q; its answer depends on the
+        board, seed and key alone, so sample(boards[k:], first_key=k *
+        per_board) is the tail of sample(boards).  status 1: the row is a valid
+        grid that keeps the givens; 0: the board has no completion (givens that
+        repeat a digit in a unit included); SDK_INVALID (-1): a byte > 9; for
+        every status but 1 the row is the input board.  boards=None with
+        per_board items samples the empty board (random_grids).
+        Every branch of the search picks uniformly among the digits left in
+        its cell (the rule is in include/sudoku_hip.h), so every completion of
+        a board can come out, but they are NOT equally likely: this is a
+        randomised search, not a uniform sampler.  seed and first_key are taken
+        mod 2^64.  max_waves > 0 caps the kernel's grid; results never depend
+        on it.  Asynchronous on the stream; one cached scratch tensor serves
+        every call, ordered like the workspace's."""
+        per_board = int(per_board)
+        if per_board < 1:
+            raise ValueError("per_board must be >= 1")
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = None if boards is None else self._dev(as_boards(boards, max_value=255))
+        n = 1 if p is None else p.shape[0]
+        items = n * per_board
+        if items > 2 ** 31 - 1:
+            raise ValueError("at most 2**31 - 1 items")
+        out = torch.empty((items, 81), dtype=torch.uint8, device=self.device)
+        status = torch.empty(items, dtype=torch.int32, device=self.device)
+        mask = (1 << 64) - 1
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_sample_scratch", int(self.lib.sdk_sample_scratch_bytes(items, int(max_waves))))
+            rc = self.lib.sdk_sample_batch(None if p is None else p.data_ptr(), out.data_ptr(), status.data_ptr(), n,
+                                           per_board, int(seed) & mask, int(first_key) & mask, sc.data_ptr(), sc.numel(),
+                                           int(max_waves), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_sample_batch")
+        return out, status
+
+    def random_grids(self, n: int, seed: int = 0, first_key: int = 0, stream=None, max_waves: int = 0) -> torch.Tensor:
+        """n random full grids as an (n, 81) uint8 tensor: sample() of the
+        empty board under keys first_key .. first_key + n - 1, with no board
+        bytes read (NULL boards).  Grid k is a function of seed and first_key
+        + k alone.  Raises if an item reports anything but a completion (the
+        call then waits for the kernel)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if n == 0:
+            return torch.empty((0, 81), dtype=torch.uint8, device=self.device)
+        grids, status = self.sample(None, seed, per_board=n, first_key=first_key, stream=stream, max_waves=max_waves)
+        if not bool((status == 1).all().item()):
+            raise SudokuHipError("a random grid of the empty board was not reported as a completion")
+        return grids
 
     def solve_batches(self, batches, outs, statuses, order="gen", stream=None, grid_waves: int = 0,
                       pipelined: bool = False):
