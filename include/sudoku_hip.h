@@ -521,6 +521,59 @@ int sdk_sample_batch(const uint8_t *d_boards /* n*81, NULL = every board empty *
                      int32_t *d_status /* items */, int64_t n, int per_board, uint64_t seed, uint64_t first_key,
                      void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
 
+/* The unique candidates of n boards: which clue, added to a board, makes it a
+ * proper puzzle (library extension, no reference counterpart).  A completion
+ * is what sdk_count_solutions_batch counts: a valid Sudoku grid that keeps
+ * the givens.  For board i, cell c and digit d:
+ *   d_once[81 i + c]  bit d-1 is set when EXACTLY one completion puts d into
+ *                     c.  For an empty cell: the board with the clue (c, d)
+ *                     added has exactly one completion.  A given's own bit is
+ *                     set exactly when the board has exactly one completion.
+ *   d_marks[81 i + c] bit d-1 is set when at least one completion puts d into
+ *                     c: byte for byte what sdk_candidates_batch writes, so
+ *                     once is a subset of marks;
+ *   d_count[i]        = min(2, completions), as sdk_candidates_batch.
+ * The answer is exact, with no cap and no truncated case: it does not depend
+ * on any search order, and the arrays of a symmetry image of a board are the
+ * images of its arrays.  Why it is exact: the leaves of one depth-first
+ * search are distinct completions.  A first search from the givens records
+ * every placement it meets (W) and every placement two of its completions
+ * share (V); if it ends before a fixed number of completions, marks = W and
+ * once = W & ~V.  Otherwise, for every placement (c, d) of the propagated
+ * board R that is not yet in V or settled, one search of R with c fixed to d
+ * counts to two: none removes the placement from R; one, then exhaustion,
+ * settles it as "exactly one"; two completions T1, T2 put T1 & T2 into V.  V
+ * only ever receives placements that two distinct completions share, a
+ * placement is settled only by an exhaustive search, and the loop ends only
+ * when every placement of R is in V or settled: marks = R, once = R & ~V.  (A
+ * completion met in one search is never paired with one met in another: they
+ * may be the same grid.)  DESIGN.md §18.
+ * A board whose givens repeat a digit in a row, column or box has no
+ * completion: zero arrays, count 0.  A byte > 9 gives zero arrays and
+ * SDK_INVALID in d_count[i]; SDK_FAULT (with zero arrays, never a partial
+ * answer) would mean a search outgrew its stack, which 81 levels make
+ * impossible.
+ * d_marks and d_count may be NULL.  d_once and d_marks need 2-byte alignment
+ * (d_count 4), d_boards none.  Inputs are never modified, no byte outside
+ * these extents is written, and the arguments are disjoint.
+ * d_scratch: at least sdk_unique_candidates_scratch_bytes(n, max_waves) bytes
+ * of device memory, 8-byte aligned, contents irrelevant: the call re-arms its
+ * queue head itself on `stream`.  SINGLE-STREAM like a workspace; the solve
+ * workspace, its counters and sdk_verify_workspace are not involved.
+ * max_waves caps the kernel's grid (0: as many waves as fit on the device at
+ * the kernel's occupancy); results never depend on it.  The scratch holds
+ * exactly 256 bytes and, per wave of min(ceil(n / 64), waves), 64 lanes x 85
+ * lines x 128 bytes (696 320 bytes a wave).
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * negative n or max_waves, a NULL pointer that is required, a misaligned
+ * pointer, scratch too small), by return code only (sdk_last_error() is not
+ * set); arguments are checked before any launch and n == 0 returns 0.
+ * sdk_unique_candidates_scratch_bytes returns 0 for negative arguments. */
+size_t sdk_unique_candidates_scratch_bytes(int64_t n, int max_waves);
+int sdk_unique_candidates_batch(const uint8_t *d_boards, uint16_t *d_once /* n*81 */,
+                                uint16_t *d_marks /* n*81, NULL ok */, int32_t *d_count /* n, NULL ok */,
+                                int64_t n, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

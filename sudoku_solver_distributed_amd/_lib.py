@@ -56,6 +56,8 @@ EXPORTS = (
     "sdk_minimize_batch",
     "sdk_sample_scratch_bytes",
     "sdk_sample_batch",
+    "sdk_unique_candidates_scratch_bytes",
+    "sdk_unique_candidates_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -149,6 +151,10 @@ def load() -> ctypes.CDLL:
     L.sdk_sample_scratch_bytes.argtypes = [i64, i32]
     L.sdk_sample_batch.restype = i32
     L.sdk_sample_batch.argtypes = [vp, vp, vp, i64, i32, ctypes.c_uint64, ctypes.c_uint64, vp, sz, i32, vp]
+    L.sdk_unique_candidates_scratch_bytes.restype = sz
+    L.sdk_unique_candidates_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_unique_candidates_batch.restype = i32
+    L.sdk_unique_candidates_batch.argtypes = [vp, vp, vp, vp, i64, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -18,8 +18,8 @@ ROOT = os.path.dirname(_HERE)
 # canon_kernels.hip, the canonical form, and rate_kernels.hip, the puzzle
 # rating, likewise units of their own, LLVM's defaults; cand_kernels.hip, the
 # exact candidates, min_kernels.hip, the minimisation, and sample_kernels.hip,
-# the random completion, units of their own with the count's scheduler,
-# DESIGN.md §15, §16 and §17)
+# the random completion, and uniq_kernels.hip, the unique candidates, units of
+# their own with the count's scheduler)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -41,7 +41,8 @@ def sources(sched: str = _SCHED):
             ("rate_kernels.hip", []),
             ("cand_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("min_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
-            ("sample_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
+            ("sample_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
+            ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
 
 
 SRCS = sources()

@@ -29,7 +29,9 @@ inline void words_of(const uint8_t *src, uint32_t (&x)[21])
 // cells (the look-ahead path only).  The put / get plane::WordStack wraps.
 // deepest: the most levels in use since the caller last zeroed it.
 struct LineStack {
-    enum { LEVELS = 83 };  // (the candidates' lanes: 81 levels, the root's line and the witnesses', plane_cand.h)
+    // (the unique candidates' lanes: 81 levels and the four set lines of
+    // plane_uniq.h; the candidates' lanes use 83 of them, plane_cand.h)
+    enum { LEVELS = 85 };
     uint32_t w[LEVELS * plane::STACK_LINE_WORDS];
     uint32_t deepest = 0;
     void put(uint32_t level, int k, uint32_t v)

@@ -26,6 +26,10 @@
 * ``make_unique(boards)`` -- boards with several completions repaired into
   proper puzzles: givens added where the GPU's exact candidates
   (BatchSolver.candidates; library extension) leave a cell open.
+* ``exchange(puzzles)`` / ``exchange_search(seeds, target)`` -- the {-1, +1}
+  clue-exchange neighbours of proper puzzles, and the breadth-first search
+  over isomorphism classes built on them, by the GPU's unique candidates
+  (BatchSolver.unique_candidates; library extension).
 * ``apply_symmetry(boards, sym)`` / ``class_ids(boards)`` -- the symmetry
   group in numbers and the isomorphism class of every board, by the GPU's
   canonical form (BatchSolver.canonical; library extension).
@@ -277,8 +281,105 @@ def make_unique(boards, device=None):
     return p, added
 
 
+# ------------------------------------------------------------- clue exchange
+# Q boards per BatchSolver.unique_candidates call inside exchange(): the bit
+# expansion of a chunk's answer holds 81 x 9 int32 per board beside the boards
+# and the int16 answer, about 200 MB for 2^16 boards
+EXCHANGE_CHUNK = 1 << 16
+
+
+def exchange(puzzles, device=None):
+    """The {-1, +1} neighbours of proper puzzles: every proper puzzle that
+    comes from one of `puzzles` by erasing one clue and adding one.  Library
+    extension, no reference counterpart; the GPU counterpart of
+    scripts/hard17/hard17_search.c, with no cap.
+
+    For every puzzle i with exactly one completion and every given cell a, let
+    Q be the puzzle without a.  Every empty cell b of Q (a included) and digit
+    v that exactly one completion of Q puts there
+    (BatchSolver.unique_candidates) gives the neighbour Q + (b, v) -- except
+    (a, the erased digit), which is puzzle i itself.  Every neighbour has
+    exactly one completion and as many clues as its parent.
+
+    Returns (neighbours (m, 81) uint8, parent (m,) int64, removed (m,) int32,
+    added_cell (m,) int32, added_digit (m,) int32), device tensors, sorted by
+    (parent, removed cell a, added cell b, added digit v).  Puzzles with no
+    completion or several, or with a byte > 9, contribute nothing.  The Q
+    boards of the whole batch are built with tensor operations and answered
+    EXCHANGE_CHUNK at a time; there is no loop over boards."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(puzzles, max_value=255))
+    dev = p.device
+    proper = solver.count_solutions(p, limit=2) == 1
+    parent, removed = torch.nonzero(proper.unsqueeze(1) & (p != 0), as_tuple=True)  # sorted by (parent, a)
+    q = p[parent]
+    rows = torch.arange(q.shape[0], dtype=torch.int64, device=dev)
+    erased = q[rows, removed].to(torch.int64)
+    q[rows, removed] = 0
+    bit = torch.arange(9, dtype=torch.int32, device=dev)
+    found = []
+    for lo in range(0, q.shape[0], EXCHANGE_CHUNK):
+        qc = q[lo:lo + EXCHANGE_CHUNK]
+        once = solver.unique_candidates(qc).to(torch.int32)
+        hit = (((once.unsqueeze(2) >> bit) & 1) != 0) & (qc == 0).unsqueeze(2)
+        k = rows[:qc.shape[0]]
+        hit[k, removed[lo:lo + EXCHANGE_CHUNK], erased[lo:lo + EXCHANGE_CHUNK] - 1] = False  # the parent itself
+        r, b, v = torch.nonzero(hit, as_tuple=True)  # sorted by (row, b, v)
+        found.append((r + lo, b, v))
+    if found:
+        r, b, v = (torch.cat(x) for x in zip(*found))
+    else:
+        r = b = v = torch.zeros(0, dtype=torch.int64, device=dev)
+    neighbours = q[r]
+    neighbours[torch.arange(r.shape[0], dtype=torch.int64, device=dev), b] = (v + 1).to(torch.uint8)
+    return neighbours, parent[r], removed[r].to(torch.int32), b.to(torch.int32), (v + 1).to(torch.int32)
+
+
+def _first_unique(boards, known: int):
+    """Indices (ascending) of the rows of `boards` from row `known` on that
+    equal no earlier row: the new classes in order of first appearance."""
+    n = boards.shape[0]
+    if not n:
+        return torch.zeros(0, dtype=torch.int64, device=boards.device)
+    uniq, ids = torch.unique(boards, dim=0, return_inverse=True)
+    first = torch.full((uniq.shape[0],), n, dtype=torch.int64, device=boards.device)
+    first.scatter_reduce_(0, ids, torch.arange(n, dtype=torch.int64, device=boards.device), reduce="amin")
+    first = torch.sort(first).values
+    return first[first >= known]
+
+
+def exchange_search(seeds, target: int, max_rounds: Optional[int] = None, device=None):
+    """Breadth-first search over isomorphism classes by clue exchange: the
+    canonical boards (BatchSolver.canonical) of the classes found, as a
+    (k, 81) uint8 device tensor -- the seeds' classes first, in the seeds'
+    order, then every new class in the order in which it first appears.
+    Library extension; what scripts/make_hard17.py does on the CPU.
+
+    Round 0's frontier is the seeds' classes (their canonical boards).  Each
+    round takes exchange(frontier), the canonical forms of its neighbours, and
+    keeps the classes not seen before, in order of first appearance; they are
+    the next frontier.  The search stops when `target` classes are known (the
+    round that reaches it is cut there, so k <= target unless the seeds alone
+    are more), when a frontier is empty, or after max_rounds rounds (None: no
+    limit).  Deterministic: the same seeds give the same tensor."""
+    solver = get_solver(device)
+    canon = solver.canonical(solver._dev(as_boards(seeds, max_value=255)))
+    classes = canon[_first_unique(canon, 0)]
+    frontier, rounds = classes, 0
+    while classes.shape[0] < target and frontier.shape[0] and (max_rounds is None or rounds < max_rounds):
+        neighbours = exchange(frontier, device=device)[0]
+        if not neighbours.shape[0]:
+            break
+        known = classes.shape[0]
+        both = torch.cat([classes, solver.canonical(neighbours)])
+        frontier = both[_first_unique(both, known)][:max(0, int(target) - known)]
+        classes = torch.cat([classes, frontier])
+        rounds += 1
+    return classes
+
+
 # ------------------------------------------------------------ symmetry classes
-_PERM3 = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+_PERM3 =((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
 CANON_SYMMETRIES = 2 * 1296 * 1296
 
 

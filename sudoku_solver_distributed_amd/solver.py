@@ -135,6 +135,7 @@ class BatchSolver:
         self._cand_scratch = None  # candidates' scratch, likewise
         self._min_scratch = None  # minimize's scratch, likewise
         self._sample_scratch = None  # sample's scratch, likewise
+        self._uniq_scratch = None  # unique_candidates' scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -336,6 +337,45 @@ class BatchSolver:
                                                n, sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
         self._rc_only(rc, "sdk_candidates_batch")
         return (marks, count) if return_count else marks
+
+    # -------------------------------------------------- unique candidates
+    def unique_candidates(self, boards, return_marks: bool = False, return_count: bool = False, stream=None,
+                          max_waves: int = 0):
+        """The candidates that exactly one completion holds, as an int16
+        (n, 81) tensor (sdk_unique_candidates_batch; library extension, no
+        reference counterpart): bit d-1 of once[i, c] is set
+        exactly when exactly ONE completion of board i -- a valid Sudoku grid
+        that keeps the givens -- puts digit d into cell c.  For an empty cell
+        that is: board i with the clue (c, d) added is a proper puzzle.  A
+        given's own bit is set exactly when the board itself has exactly one
+        completion.  There is no cap and no truncated case; the answer depends
+        on no search order and the answer of a symmetry image of a board is
+        the image of its answer.
+        return_marks: also the int16 (n, 81) tensor candidates() returns, bit
+        for bit (at least one completion; once is a subset of it);
+        return_count: also an int32 (n,) tensor, min(2, completions), as
+        candidates() gives it; SDK_INVALID (-1, with zero arrays) for a byte
+        > 9.  Givens that repeat a digit in a unit have no completion.  The
+        optional outputs follow once in this order.  max_waves > 0 caps the
+        kernel's grid; results never depend on it.  Asynchronous on the
+        stream; one cached scratch tensor serves every call, ordered like the
+        workspace's."""
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        once = torch.empty((n, 81), dtype=torch.int16, device=self.device)
+        marks = torch.empty((n, 81), dtype=torch.int16, device=self.device) if return_marks else None
+        count = torch.empty(n, dtype=torch.int32, device=self.device) if return_count else None
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_uniq_scratch", int(self.lib.sdk_unique_candidates_scratch_bytes(n, int(max_waves))))
+            rc = self.lib.sdk_unique_candidates_batch(p.data_ptr(), once.data_ptr(),
+                                                      marks.data_ptr() if return_marks else None,
+                                                      count.data_ptr() if return_count else None, n, sc.data_ptr(),
+                                                      sc.numel(), int(max_waves), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_unique_candidates_batch")
+        out = (once,) + ((marks,) if return_marks else ()) + ((count,) if return_count else ())
+        return out if len(out) > 1 else once
 
     # ----------------------------------------------------------- minimize
     def minimize(self, boards, order=None, max_empty: int = 81, probe: bool = False, return_removed: bool = False,
