@@ -224,6 +224,12 @@ def test_symmetry_images_keep_rating_and_open(solver, fx):
     assert np.array_equal(r, fx["rating"][idx]) and np.array_equal(o, fx["open"][idx])
     count = lambda a: np.unpackbits(np.ascontiguousarray(a).view(np.uint8), axis=1).sum(1)
     assert np.array_equal(count(m), count(fx["marks"][idx]))
+    # and the marks bit for bit, under symmetries whose maps are known (symmetry_cases.py)
+    import symmetry_cases as S
+    syms = [S.random_symmetry(rng) for _ in idx]
+    r, o, m = gpu_rate(solver, np.stack([S.image_board(fx["boards"][i], s) for i, s in zip(idx, syms)]))
+    assert np.array_equal(r, fx["rating"][idx]) and np.array_equal(o, fx["open"][idx])
+    assert np.array_equal(m, np.stack([S.image_marks(fx["marks"][i], s) for i, s in zip(idx, syms)]))
 
 
 def test_rated_batch(solver):

@@ -140,17 +140,21 @@ def _popcount(t):
 
 def test_symmetry_images_have_as_many_bits(solver, fx):
     """16 boards with several completions and their gen.apply_symmetry images:
-    the total popcounts of once and of marks are equal."""
+    the total popcounts of once and of marks are equal, and once and marks are
+    the images of the fixture's, bit for bit (symmetry_cases.from_number)."""
+    import symmetry_cases as S
     from sudoku_solver_distributed_amd.gen import apply_symmetry
     sel = np.nonzero((fx["count"] == 2) & (fx["once"] != 0).any(1))[0][:16]
     assert len(sel) == 16
     sym = np.random.default_rng(5).integers(0, 2 * 1296 * 1296, size=16)
-    images, _ = apply_symmetry(fx["boards"][sel], sym)
+    images, maps = apply_symmetry(fx["boards"][sel], sym)
     assert (images != fx["boards"][sel]).any(1).all()
     o, m, c = gpu_uniq(solver, images)
     for k, i in enumerate(sel):
         assert _popcount(torch.from_numpy(o[k].astype(np.int32))) == _popcount(torch.from_numpy(fx["once"][i].astype(np.int32)))
         assert _popcount(torch.from_numpy(m[k].astype(np.int32))) == _popcount(torch.from_numpy(fx["marks"][i].astype(np.int32)))
+        s = S.from_number(sym[k], maps[k])
+        assert np.array_equal(o[k], S.image_marks(fx["once"][i], s)) and np.array_equal(m[k], S.image_marks(fx["marks"][i], s))
     assert (c == 2).all()
 
 
