@@ -23,6 +23,8 @@ for r in $(seq 1 ${R:-2}); do
       rc=$?
     fi
     [ $rc -eq 0 ] || { echo "$cfg rc=$rc"; exit $rc; }
+    # RAW=<file>: the bench's own line, kept whole, appended to that file
+    [ -n "$RAW" ] && echo "{\"round\": $r, \"cfg\": \"$cfg\", \"bench_args\": \"${BENCH_ARGS}\", \"result\": $out}" >> "$RAW"
     echo "$out" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('round $r $cfg', 'Mb/s=%.1f' % (d['value']/1e6), 'ms=%.3f' % d['ms_per_step'], 'kern_ms=%.3f' % d['roofline']['kernel_ms'], 'passes=%.2f' % d.get('sweeps_per_board', 0), 'guess=%.3f' % d.get('guesses_per_board', 0))"
   done
 done

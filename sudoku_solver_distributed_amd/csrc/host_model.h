@@ -88,6 +88,13 @@ struct Counts {
     uint64_t guesses, passes_lane, passes_wide;  // guesses: lane and wide together
 };
 enum : uint32_t { LANE_ONLY = 0xFFFFFFFFu };  // lane_guesses: no hand-over
+// per board (solve_batch's `info`): lane passes, whether the board ended by the
+// root rule (plane::search_step_impl's root_full), whether grid_complete()
+// then rejected its all-single root
+struct BoardInfo {
+    uint32_t passes;
+    uint8_t by_rule, rejected;
+};
 
 // Solve each board.  The lane phase steps one pass and one search step per
 // iteration, as a lane of plane_kernel does: the look-ahead pass the kernel
@@ -98,10 +105,13 @@ enum : uint32_t { LANE_ONLY = 0xFFFFFFFFu };  // lane_guesses: no hand-over
 // solver continues from the same planes, stack, depth and search mode (Det,
 // und and nd dropped, as the kernel's tail drops them); LANE_ONLY: never.
 // out: the completion, or the input back.  status: 1 solved, 0 no completion,
-// -1 a byte > 9, 2 left to the wave kernel (clashing givens or a search deeper
-// than max_depth <= LineStack::LEVELS).
+// -1 a byte > 9, 2 left to the wave kernel (clashing givens, a search deeper
+// than max_depth <= LineStack::LEVELS, or -- root_full, the look-ahead path
+// only, as the plane kernel's unordered lane loop runs it -- an all-single
+// root that plane::grid_complete rejects, as the kernel's outbox flush does).
 inline void solve_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_t n, bool ahead, uint32_t lane_guesses,
-                        int node_order, uint32_t max_depth, uint32_t mrv_after, Counts &c)
+                        int node_order, uint32_t max_depth, uint32_t mrv_after, Counts &c, bool root_full = false,
+                        BoardInfo *info = nullptr)
 {
     static LineStack lines;
     const plane::WordStack<LineStack> ls = {lines};
@@ -121,10 +131,15 @@ inline void solve_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_
         for (int b = 0; b < 3; ++b) und[b] = plane::ROWS & ~nd[b];  // (plane::pass computes its own und)
         uint32_t depth = 0, lg = 0, mst = 0;
         int s = plane::S_CONT;
+        bool by_rule = false;
+        const uint64_t p0 = c.passes_lane;
+        if (info) info[i] = {0u, 0, 0};
         while (s == plane::S_CONT && lg < lane_guesses) {
             if (ahead) {
                 const int r = plane::pass_ahead(B, und, nd);
-                s = plane::search_step_ahead(B, und, nd, r, depth, mst, ls, node_order, max_depth, mrv_after, lg);
+                s = plane::search_step_ahead(B, und, nd, r, depth, mst, ls, node_order, max_depth, mrv_after, lg,
+                                             root_full);
+                by_rule = s == plane::S_SOLVED && r == plane::OPEN;  // (only the rule ends an OPEN pass)
             } else {
                 const int r = plane::pass(B, und);
                 s = plane::search_step(B, und, r, depth, mst, ls, node_order, max_depth, mrv_after, lg);
@@ -132,6 +147,15 @@ inline void solve_batch(const uint8_t *in, uint8_t *out, int32_t *status, int64_
             c.passes_lane++;
         }
         c.guesses += lg;
+        if (info) {
+            info[i].passes = (uint32_t)(c.passes_lane - p0);
+            info[i].by_rule = by_rule;
+        }
+        if (by_rule && !plane::grid_complete(B)) {
+            if (info) info[i].rejected = 1;
+            status[i] = 2;
+            continue;
+        }
         if (s != plane::S_CONT) {
             if (s == plane::S_SOLVED) plane::store_values(B, [&](int cell, uint32_t v) { dst[cell] = (uint8_t)v; });
             status[i] = s == plane::S_SOLVED ? 1 : s == plane::S_NONE ? 0 : 2;

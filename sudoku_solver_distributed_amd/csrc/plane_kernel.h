@@ -88,6 +88,15 @@
 #ifndef SDK_PLANE_LDS_PAD
 #define SDK_PLANE_LDS_PAD 0
 #endif
+// 1: an unordered launch's lane loop takes a board whose ROOT is all single
+// as solved at once, without the verifying pass (plane::search_step_impl's
+// root_full), and the outbox flush tests every board it stores with
+// plane::grid_complete, a board per lane: one that fails is deferred to the
+// wave kernel.  0: the verifying pass everywhere, the status word written
+// when a board enters the outbox (A/B builds)
+#ifndef SDK_PLANE_ROOTFULL
+#define SDK_PLANE_ROOTFULL 1
+#endif
 
 // Cooperative board I/O.  Loads and stores run for one board at a time over
 // the whole wave, in the band-word layout: lane l's slot 0 is bit (l & 31)
@@ -334,15 +343,34 @@ __device__ __forceinline__ uint32_t plane_unguard(uint32_t v)
 // and 20 whole when the span starts / ends on a dword boundary, byte by
 // byte otherwise (they hold neighbouring boards' bytes).  Byte expansion:
 // value bit k of 4 consecutive cells, a nibble of the slice's 81-bit cell
-// stream, spreads to bit k of 4 bytes with one multiply (bit i -> bit 8i).
+// SDK_PLANE_ROOTFULL: the lane first tests that its board is a completion
+// (plane::grid_complete: a root taken as solved without its verifying pass
+// may be none, on a board that has no completion or whose givens clash); if
+// so it writes the bytes and the status SDK_SOLVED, else nothing of the
+// output and the board goes to the wave kernel (plane_defer), which gives the
+// literal answer.  The lane counts the board (solved / fin or deferred) with
+// the status word it writes.  (A deferred board's guesses need no taking back:
+// a root board made none, and a board that guessed passed its verifying pass.)
 template <class IO>
-__device__ __forceinline__ void plane_flush_outbox(const uint32_t *outbox, uint32_t count, int lane, const IO &io)
+__device__ __forceinline__ void plane_flush_outbox(const uint32_t *outbox, uint32_t count, int lane, const IO &io,
+                                                   unsigned long long *__restrict__ ws, int64_t *__restrict__ defer_list,
+                                                   uint32_t &solved, uint32_t &fin, uint32_t &deferred)
 {
     if ((uint32_t)lane < count) {
         const sdk_v4u *rec = (const sdk_v4u *)(outbox + PLANE_OB_WORDS * lane);
         const sdk_v4u r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
         const uint32_t V[4][3] = {{r0.x, r0.y, r0.z}, {r0.w, r1.x, r1.y}, {r1.z, r1.w, r2.x}, {r2.y, r2.z, r2.w}};
         const int64_t pb = ((int64_t)r3.y << 32) | r3.x;
+#if SDK_PLANE_ROOTFULL
+        if (!plane::grid_complete(V)) {
+            plane_defer(io.stat(pb), pb, ws, defer_list);
+            deferred++;
+            return;
+        }
+        *io.stat(pb) = SDK_SOLVED;
+        solved++;
+        fin++;
+#endif
         uint8_t *dst = io.dst(pb);
         const uint32_t sh = (uint32_t)(uintptr_t)dst & 3u;
         uint32_t *dw = (uint32_t *)(dst - sh);
@@ -858,12 +886,14 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
             const uint64_t st_s0 = __builtin_amdgcn_s_memtime();
 #endif
             uint64_t m = __builtin_amdgcn_ballot_w64(state == PL_SOLVED);
+#if !SDK_PLANE_ROOTFULL
             solved += state == PL_SOLVED;
             fin += state == PL_SOLVED;
+#endif
             if (m) {
                 const uint32_t ns = (uint32_t)__builtin_popcountll(m);
                 if (ob_count + ns > (uint32_t)PLANE_OUTBOX) {
-                    plane_flush_outbox(outbox, ob_count, lane, io);
+                    plane_flush_outbox(outbox, ob_count, lane, io, ws, defer_list, solved, fin, deferred);
                     ob_count = 0;
                 }
                 if (state == PL_SOLVED) {
@@ -880,7 +910,9 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
                     rec[1] = (sdk_v4u){V[1][1], V[1][2], V[2][0], V[2][1]};
                     rec[2] = (sdk_v4u){V[2][2], V[3][0], V[3][1], V[3][2]};
                     rec[3] = (sdk_v4u){(uint32_t)p, (uint32_t)(p >> 32), 0u, 0u};
+#if !SDK_PLANE_ROOTFULL
                     *io.stat(p) = SDK_SOLVED;  // every solved lane its own, one store
+#endif
                 }
                 ob_count += ns;
             }
@@ -894,8 +926,10 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
                 if (!cancelled && plane_givens_clash(io.src(pi), c0, c1)) {
                     // rules B/C are unsound on givens that repeat a digit in a
                     // unit: "no completion" is the packed kernel's call.  (A
-                    // SOLVED result needs every unit to hold every digit, so
-                    // such givens never reach the store above.)
+                    // SOLVED result needs every unit to hold every digit --
+                    // the verifying pass's test, or the flush's
+                    // grid_complete on a root taken without one -- so such
+                    // givens are never stored as solved.)
                     if (lane == i) {
                         plane_defer(io.stat(pi), pi, ws, defer_list);
                         deferred++;
@@ -1074,8 +1108,10 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
         const uint32_t st_d0 = depth;
         const uint64_t st_s0 = __builtin_amdgcn_s_memtime();
 #endif
+        // (unordered launches only: in ordered mode a provisional SOLVED would
+        // lower WS_BEST and cancel higher boards before the flush's test)
         const int s = plane::search_step_ahead(B, und, nd, r, depth, mst, stk, node_order, PLANE_MAX_DEPTH, mrv_after,
-                                               bguess);
+                                               bguess, SDK_PLANE_ROOTFULL && best == nullptr);
 #if SDK_PLANE_STAMPS
         st_step += __builtin_amdgcn_s_memtime() - st_s0;
         st_push += wany(bguess != gb) ? 1u : 0u;
@@ -1095,7 +1131,7 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
             state = PL_IDLE;
         }
     }
-    if (ob_count) plane_flush_outbox(outbox, ob_count, lane, io);
+    if (ob_count) plane_flush_outbox(outbox, ob_count, lane, io, ws, defer_list, solved, fin, deferred);
 #if SDK_PLANE_STAMPS
     const uint64_t st_tt = __builtin_amdgcn_s_memtime();
     const uint64_t st_t3 = __builtin_amdgcn_s_memrealtime();  // the lane loop ended

@@ -780,6 +780,92 @@ PS_FN void store_values(const Board &B, Put put)
     }
 }
 
+// ---- a complete grid, from its value bit-slices
+// a three-input truth table on the host (bit 4a + 2b + c of tt = f(a, b, c):
+// v_bitop3_b32's convention, src0 = 0xF0, src1 = 0xCC, src2 = 0xAA)
+PS_FN uint32_t tt3(unsigned tt, uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r = 0;
+    for (int i = 0; i < 8; ++i)
+        if ((tt >> i) & 1u) r |= ((i & 4) ? a : ~a) & ((i & 2) ? b : ~b) & ((i & 1) ? c : ~c);
+    return r;
+}
+// The cells of a band holding value D + 1 (1..9), from the band's four value
+// bit-slices: two v_bitop3.  A value 1..9 has a set bit, so one slice enters
+// uncomplemented and the word's guard bits stay 0.
+template <int D>
+PS_FN uint32_t value_word(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3)
+{
+    constexpr unsigned v = D + 1;
+    constexpr unsigned TT = ((v & 1) ? 0xF0u : 0x0Fu) & ((v & 2) ? 0xCCu : 0x33u) & ((v & 4) ? 0xAAu : 0x55u);
+    static_assert(v >= 1 && v <= 9, "a digit 1..9");
+    const uint32_t t = PS_BOP3(TT, v0, v1, v2, tt3(TT, v0, v1, v2));
+    return (v & 8) ? (t & v3) : andn(t, v3);
+}
+// One digit's part of grid_complete(): row / column / box presence of the
+// digit's plane words y[b], ANDed into the accumulators (pass_body's tests)
+PS_FN void grid_digit(const uint32_t (&y)[3], uint32_t &rowall, uint32_t &colall, uint32_t &boxall)
+{
+    uint32_t o[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        rowall &= y[b] + ROWS;                          // row guard set iff the row has a place
+        o[b] = or3(y[b], y[b] >> 10, y[b] >> 20);       // bits 0-8: columns with a place in the band
+        boxall &= or3(o[b], o[b] >> 1, o[b] >> 2);      // bits 0 / 3 / 6: boxes with a place
+    }
+    colall &= or3(o[0], o[1], o[2]);
+}
+template <int D>
+PS_FN void grid_digits(uint32_t (&V)[4][3], uint32_t &rowall, uint32_t &colall, uint32_t &boxall)
+{
+    uint32_t y[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) y[b] = value_word<D>(V[0][b], V[1][b], V[2][b], V[3][b]);
+    grid_digit(y, rowall, colall, boxall);
+    if constexpr (D > 0) {
+        // the next digit starts from the slices as they stand here, so the
+        // digits' independent chains run one after the other (few registers)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) PS_PIN(V[k][b]);
+        PS_PIN(rowall);
+        PS_PIN(colall);
+        PS_PIN(boxall);
+        grid_digits<D - 1>(V, rowall, colall, boxall);
+    }
+}
+// Is the grid with value bit-slices V[k][b] (bit k of the value at each cell,
+// every cell holding one value) a completion: does every digit have a place
+// in every row, column and box?  Nine digits present in a unit of nine cells
+// stand there once each.  All nine are tested: presence of eight alone would
+// accept a unit holding one of them twice and the ninth not at all.  Digit by
+// digit, three plane words and three accumulators live; ~35 VALU per digit.
+PS_FN bool grid_complete(const uint32_t (&slices)[4][3])
+{
+    uint32_t rowall = GUARDS, colall = 0x1FFu, boxall = BOXC;
+    uint32_t V[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) V[k][b] = slices[k][b];
+    grid_digits<8>(V, rowall, colall, boxall);
+    return or3((rowall & GUARDS) ^ GUARDS, (colall & 0x1FFu) ^ 0x1FFu, (boxall & BOXC) ^ BOXC) == 0;
+}
+// the same on a board whose cells are all determined
+PS_FN bool grid_complete(const Board &B)
+{
+    uint32_t V[4][3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        V[0][b] = B.P[0][b] | B.P[2][b] | B.P[4][b] | B.P[6][b] | B.P[8][b];
+        V[1][b] = B.P[1][b] | B.P[2][b] | B.P[5][b] | B.P[6][b];
+        V[2][b] = B.P[3][b] | B.P[4][b] | B.P[5][b] | B.P[6][b];
+        V[3][b] = B.P[7][b] | B.P[8][b];
+    }
+    return grid_complete(V);
+}
+
 // stack level: the 27 plane words + the branch entry; on the look-ahead path
 // (pass_ahead) the level's undetermined cells follow in words 28-30 of a
 // 32-word line
@@ -849,13 +935,26 @@ PS_FN bool root_counts(int mode, uint32_t depth, uint32_t mrv_after, uint32_t u0
 // is pending (every determined cell removed from its peers), so a guess or a
 // backtrack leaves nd[] = the one cell it fixed, and a return to the root
 // nd[] = 0: no Det reset, and no repeat of rule B for all determined cells.
+//
+// root_full (wave-uniform; off for every caller that does not ask): a board
+// whose ROOT is all single after an OPEN pass -- M_WALK at depth 0: no guess
+// was made, a fix leaves depth >= 1 and a last-digit pop keeps level 0 -- is
+// S_SOLVED at once, without the verifying pass.  Rules A-D only delete places
+// no completion uses, so such a root of a board that has a completion IS that
+// completion; a board without one (or with clashing givens) can reach a
+// false all-single root, so the CALLER must test the answer with
+// grid_complete() and hand a board that fails it to the wave kernel.  Inside
+// a guessed branch two cells that became single in one pass can share a digit
+// in a unit, and the verifying pass is what finds it: every other mode and
+// depth keeps it.
 template <bool AHEAD, class Stack>
 PS_FN int search_step_impl(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], int r, uint32_t &depth, uint32_t &mst,
                            const Stack &stk, int node_order, uint32_t max_depth, uint32_t mrv_after,
-                           uint32_t &guesses)
+                           uint32_t &guesses, bool root_full = false)
 {
     mst++;
     int mode = mst_mode(mst);
+    if (root_full && r == OPEN && mode == M_WALK && depth == 0 && or3(und[0], und[1], und[2]) == 0) return S_SOLVED;
     if (r == STUCK && root_counts(mode, depth, mrv_after, und[0], und[1], und[2])) {
         mode = M_COUNT;  // count from the root, branching right here
         mst = mst_set_mode(mst, M_COUNT);
@@ -985,9 +1084,10 @@ PS_FN int search_step(Board &B, const uint32_t (&und)[3], int r, uint32_t &depth
 template <class Stack>
 PS_FN int search_step_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], int r, uint32_t &depth, uint32_t &mst,
                             const Stack &stk, int node_order, uint32_t max_depth, uint32_t mrv_after,
-                            uint32_t &guesses)
+                            uint32_t &guesses, bool root_full = false)
 {
-    return search_step_impl<true>(B, und, nd, r, depth, mst, stk, node_order, max_depth, mrv_after, guesses);
+    return search_step_impl<true>(B, und, nd, r, depth, mst, stk, node_order, max_depth, mrv_after, guesses,
+                                  root_full);
 }
 
 // the step's stack interface over a word stack with put(level, k, v) / get(level, k)
@@ -1052,9 +1152,11 @@ PS_FN int solve(Board &B, Stack &stk, int node_order, uint32_t max_depth, Stats 
 // The same driver on the look-ahead pass (the plane kernel's lane loop):
 // und[] / nd[] start from rule A on the board as loaded (a fresh board's
 // determined cells are its givens).  The stack's lines hold STACK_LINE_WORDS
-// words.
+// words.  root_full: search_step_impl's rule; an all-single root that is no
+// completion returns -1 (the wave kernel's board).
 template <typename Stack>
-PS_FN int solve_ahead(Board &B, Stack &stk, int node_order, uint32_t max_depth, Stats &st, uint32_t mrv_after = 0)
+PS_FN int solve_ahead(Board &B, Stack &stk, int node_order, uint32_t max_depth, Stats &st, uint32_t mrv_after = 0,
+                      bool root_full = false)
 {
     const WordStack<Stack> ws = {stk};
     uint32_t depth = 0, mst = 0, und[3], nd[3];
@@ -1063,8 +1165,10 @@ PS_FN int solve_ahead(Board &B, Stack &stk, int node_order, uint32_t max_depth, 
     for (;;) {
         const int r = pass_ahead(B, und, nd);
         st.passes++;
-        const int s = search_step_ahead(B, und, nd, r, depth, mst, ws, node_order, max_depth, mrv_after, st.guesses);
+        const int s = search_step_ahead(B, und, nd, r, depth, mst, ws, node_order, max_depth, mrv_after, st.guesses,
+                                        root_full);
         if (s == S_CONT) continue;
+        if (s == S_SOLVED && root_full && r == OPEN && !grid_complete(B)) return -1;
         return s == S_SOLVED ? 1 : s == S_NONE ? 0 : -1;
     }
 }
