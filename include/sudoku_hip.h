@@ -574,6 +574,73 @@ int sdk_unique_candidates_batch(const uint8_t *d_boards, uint16_t *d_once /* n*8
                                 uint16_t *d_marks /* n*81, NULL ok */, int32_t *d_count /* n, NULL ok */,
                                 int64_t n, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
 
+/* Count the completions of n boards exactly, without a cap (library extension,
+ * no reference counterpart).  A completion is what
+ * sdk_count_solutions_batch counts: a valid grid that keeps the givens.  The
+ * search tree of a board is cut into tasks on the GPU and shared over every
+ * lane of the grid, so one heavy board uses the whole device.
+ *   d_status[i] == SDK_EXACT_DONE:    d_count[i] is the exact number of
+ *       completions of board i.  Givens that repeat a digit in a row, column
+ *       or box give 0 with SDK_EXACT_DONE: an exact zero, as in the capped
+ *       count.
+ *   d_status[i] == SDK_EXACT_PARTIAL: the call ran max_rounds rounds and the
+ *       board still had open tasks.  d_count[i] is the number of distinct
+ *       completions met so far: a true lower bound, NOT reproducible from run
+ *       to run (it depends on which lanes got how far).
+ *   d_status[i] == SDK_INVALID:       a byte > 9; d_count[i] = 0.
+ *   d_status[i] == SDK_FAULT:         a search outgrew its stack, which 81
+ *       levels make impossible; d_count[i] = 0, never a partial number.
+ * Boards that finished are unaffected by boards that did not.  For a board
+ * with SDK_EXACT_DONE the answer never depends on slice, max_tasks,
+ * max_waves, max_rounds, the batch the board came in or its place in it.
+ * The call is a sequence of rounds, each one launch of the same grid.  In a
+ * round a lane runs about `slice` propagation passes (fewer than slice + 82:
+ * it stops at its first dead end past `slice`), then hands the open levels of
+ * its search to a task list for the next round, or keeps them when the list
+ * is full.  No lane or wave ever waits for another, so every launch is
+ * bounded by construction.  max_tasks: the capacity of each of the two task
+ * lists (the one a round reads, the one it writes; they share one ring), 0:
+ * four tasks per lane of the grid; at most 2^31 - 1.  max_waves: the grid, the
+ * same for every n (0: as many waves as fit on the device at the kernel's
+ * occupancy).
+ * d_count cannot overflow: a completion costs at least one propagation pass
+ * of one lane, a call runs fewer than max_rounds * (slice + 82) passes a
+ * lane, and a call whose max_rounds * (slice + 82) * 64 * waves reaches 2^63
+ * is refused as a bad argument (with a full grid of 2^18 lanes that leaves
+ * max_rounds * slice up to about 2^45, years of device time).
+ * SYNCHRONOUS on `stream`, like sdk_read_stats: after every round the call
+ * reads one 64-byte line of counters back (the number of open tasks decides
+ * whether another round runs), and it returns when the results are written.
+ * Thread-safe: the library runs one such launch sequence at a time.
+ * stats (HOST memory, may be NULL) receives four values: rounds launched,
+ * task lines donated, lane parks (a lane kept its levels because the list had
+ * no room), and the most passes any lane ran in one round.
+ * d_count needs 8-byte alignment, d_status 4, d_boards none.  Inputs are never
+ * modified, no byte outside these extents is written, and the arguments are
+ * disjoint.
+ * d_scratch: at least sdk_count_exact_scratch_bytes(n, max_waves, max_tasks)
+ * bytes of device memory, 16-byte aligned, contents irrelevant: the call arms
+ * it itself on `stream`.  SINGLE-STREAM like a workspace; the solve workspace,
+ * its counters and sdk_verify_workspace are not involved.  With W waves and
+ * T = max_tasks (or 256 W for 0) the scratch holds exactly
+ *   256 + W * 64 * 81 * 128 + 2 T * 128 + W * 64 * 8 + 4 n rounded up to 16
+ * bytes: the counters, the lanes' stack lines, the task lines, the lanes'
+ * park words, the boards' open-task counters.  About 2.9 GB for a full grid
+ * of 4096 waves.
+ * Returns 0 / -1 (HIP error) / -2 (bad arguments: slice < 1, max_rounds < 1,
+ * max_tasks out of range, a pass budget of 2^63, negative n or max_waves, n > 2^31 - 1, a NULL
+ * pointer that is required, a misaligned pointer, scratch too small), by
+ * return code only (sdk_last_error() is not set); arguments are checked
+ * before any launch and n == 0 returns 0 before any other check.
+ * sdk_count_exact_scratch_bytes returns 0 for bad arguments. */
+#define SDK_EXACT_DONE 1    /* d_count[i] is the exact number of completions */
+#define SDK_EXACT_PARTIAL 2 /* the round budget ran out: d_count[i] is a lower bound */
+size_t sdk_count_exact_scratch_bytes(int64_t n, int max_waves, int64_t max_tasks);
+int sdk_count_exact_batch(const uint8_t *d_boards, int64_t *d_count /* n */, int32_t *d_status /* n */,
+                          int64_t n, int slice, int max_rounds, int64_t max_tasks, void *d_scratch,
+                          size_t scratch_bytes, int max_waves, void *stream,
+                          int64_t *stats /* HOST, 4 values, NULL ok */);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -58,6 +58,8 @@ EXPORTS = (
     "sdk_sample_batch",
     "sdk_unique_candidates_scratch_bytes",
     "sdk_unique_candidates_batch",
+    "sdk_count_exact_scratch_bytes",
+    "sdk_count_exact_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -68,6 +70,8 @@ SDK_RATE_MAX_LEVEL = 4  # sdk_rate_batch: the deepest rule level (trial eliminat
 SDK_RATE_NOT_RUN = -2  # ... and the open count of a level above max_level
 SDK_MIN_GREEDY = 0  # sdk_minimize_batch: erase givens turn by turn while one completion is left
 SDK_MIN_PROBE = 1   # ... or test every given alone against the input board
+SDK_EXACT_DONE = 1     # sdk_count_exact_batch: the count is exact
+SDK_EXACT_PARTIAL = 2  # ... or a lower bound: the round budget ran out
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -155,6 +159,10 @@ def load() -> ctypes.CDLL:
     L.sdk_unique_candidates_scratch_bytes.argtypes = [i64, i32]
     L.sdk_unique_candidates_batch.restype = i32
     L.sdk_unique_candidates_batch.argtypes = [vp, vp, vp, vp, i64, vp, sz, i32, vp]
+    L.sdk_count_exact_scratch_bytes.restype = sz
+    L.sdk_count_exact_scratch_bytes.argtypes = [i64, i32, i64]
+    L.sdk_count_exact_batch.restype = i32
+    L.sdk_count_exact_batch.argtypes = [vp, vp, vp, i64, i32, i32, i64, vp, sz, i32, vp, ctypes.POINTER(ctypes.c_int64)]
     _lib = L
     return L
 

@@ -19,7 +19,8 @@ ROOT = os.path.dirname(_HERE)
 # rating, likewise units of their own, LLVM's defaults; cand_kernels.hip, the
 # exact candidates, min_kernels.hip, the minimisation, and sample_kernels.hip,
 # the random completion, and uniq_kernels.hip, the unique candidates, units of
-# their own with the count's scheduler)
+# their own with the count's scheduler, DESIGN.md §15, §16, §17 and §18;
+# exact_kernels.hip, the exact count shared over the grid, likewise, §20)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -42,7 +43,8 @@ def sources(sched: str = _SCHED):
             ("cand_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("min_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("sample_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
-            ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
+            ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
+            ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
 
 
 SRCS = sources()

@@ -1,0 +1,417 @@
+// exact_kernels.hip -- translation unit of the exact, uncapped completion
+// count (plane_exact.h): exact_kernel, its two small companions and the C ABI
+// entries (sdk_count_exact_scratch_bytes, sdk_count_exact_batch).  A unit of
+// its own, like count_kernels.hip: the other units, their flags and the solve
+// workspace are not involved (common.h is included for cached_occupancy
+// alone).
+//
+// exact_kernel is one ROUND: count_kernel's shape, one task per LANE,
+// persistent one-wave workgroups, the same grid in every round of a call.  A
+// lane first looks at its park word and resumes the stack it left in the
+// round before.  When EXACT_REFILL lanes of a wave want a task (or none is
+// busy) lane 0 claims that many with ONE agent-scope fetch-add on the round's
+// claim counter: lines of the ring's readable part [head0, limit) first, and,
+// that part handed out, boards not yet started with one more fetch-add on the
+// board counter.  A lane runs plane::exact_iter per loop iteration and counts
+// its passes; at `slice` it takes no new task and stops at its next DEAD
+// verdict, donates its levels to the ring (plane::exact_donate) or parks
+// them, and flushes its `found` into d_count with one 64-bit atomic add.  No
+// lane or wave waits for another: the ring's part written in a round is read
+// in the next launch at the earliest, a reservation is a bounded number of
+// compare-and-swap attempts, and a wave leaves when its lanes have stopped.
+// A round therefore ends after fewer than slice + EXACT_RUN_MAX passes a lane.
+//
+// Between rounds the host reads the head block back (open tasks, claim
+// counter, write position), advances head0 and limit, and re-arms the claim
+// counter in stream order.  exact_init_kernel arms a call (counts, statuses,
+// open-task counters, park words, head block); exact_final_kernel writes the
+// statuses from the per-board open-task counters.
+//
+// Scratch: [0, 256) the head block (plane_exact.h's XH_ words), then per wave
+// 64 lanes x COUNT_MAX_DEPTH stack lines of 128 bytes (plane_stack.h's
+// PlaneStack; each wave addresses its own lines through a buffer descriptor
+// that covers exactly them), the ring's lines, 8 bytes a lane of park words,
+// 4 bytes a board of open-task counters.
+#include <mutex>
+
+#include "common.h"
+#include "plane_exact.h"
+#include "plane_stack.h"
+
+#define EXACT_THREADS 64    // one wave per workgroup
+#define EXACT_WAVES_PER_EU 4
+#define EXACT_HEAD_BYTES 256
+#define EXACT_LANE_BYTES ((uint32_t)plane::COUNT_MAX_DEPTH * 128u)
+#define EXACT_WAVE_BYTES (64u * EXACT_LANE_BYTES)
+#define EXACT_MAX_BOARDS ((int64_t)INT32_MAX)
+#define EXACT_MAX_TASKS ((int64_t)INT32_MAX)
+static_assert(plane::XH_WORDS * 8 == EXACT_HEAD_BYTES, "head block");
+
+// The 21 words of the board at `src` (any alignment): the 21 aligned dwords
+// that hold its 81 bytes (byte 80 lies in dword 20 for every alignment, so
+// every dword read holds a byte of the board), funnel-shifted into place.
+// Only byte 0 of x[20] is the board's.
+__device__ __forceinline__ void exact_load_words(const uint8_t *src, uint32_t (&x)[21])
+{
+    const uintptr_t a = (uintptr_t)src;
+    const uint32_t *d = (const uint32_t *)(a & ~(uintptr_t)3);
+    const uint32_t r = ((uint32_t)a & 3u) * 8u;
+    uint32_t lo = d[0];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) {
+        const uint32_t hi = d[k + 1];
+        x[k] = r ? __builtin_amdgcn_alignbit(hi, lo, r) : lo;
+        lo = hi;
+    }
+    x[20] = lo >> r;
+}
+
+struct ExactAtomics {
+    __device__ __forceinline__ uint64_t load(const uint64_t *p) const
+    {
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ bool cas(uint64_t *p, uint64_t &expected, uint64_t desired) const
+    {
+        return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// what a round's lanes share: the head block and the ring (plane_exact.h)
+struct ExactShared {
+    uint64_t *head;
+    uint32_t *ring;
+    uint64_t cap, head0, limit, target;
+    uint32_t slot0;  // head0's slot
+    __device__ __forceinline__ bool wants() const { return ExactAtomics().load(&head[plane::XH_TAIL]) - limit < target; }
+    __device__ __forceinline__ uint64_t reserve(uint32_t k) const
+    {
+        return plane::exact_reserve(ExactAtomics(), &head[plane::XH_TAIL], head0, cap, k);
+    }
+    // the line of a position in [head0, head0 + cap)
+    __device__ __forceinline__ sdk_v4u *line(uint64_t pos) const
+    {
+        uint64_t s = (uint64_t)slot0 + (pos - head0);
+        if (s >= cap) s -= cap;
+        return (sdk_v4u *)(ring + s * plane::STACK_LINE_WORDS);
+    }
+    __device__ __forceinline__ void put(uint64_t pos, plane::Board &B, const uint32_t (&und)[3], uint32_t entry,
+                                        uint32_t board) const
+    {
+        sdk_v4u *w = line(pos);
+        plane::pin_board(B);
+#define XQ(a, b, c, d) (sdk_v4u){B.P[a / 3][a % 3], B.P[b / 3][b % 3], B.P[c / 3][c % 3], B.P[d / 3][d % 3]}
+        w[0] = XQ(0, 1, 2, 3);
+        w[1] = XQ(4, 5, 6, 7);
+        w[2] = XQ(8, 9, 10, 11);
+        w[3] = XQ(12, 13, 14, 15);
+        w[4] = XQ(16, 17, 18, 19);
+        w[5] = XQ(20, 21, 22, 23);
+#undef XQ
+        w[6] = (sdk_v4u){B.P[8][0], B.P[8][1], B.P[8][2], entry};
+        w[7] = (sdk_v4u){und[0], und[1], und[2], board};
+    }
+    __device__ __forceinline__ uint32_t get(uint64_t pos, plane::Board &B, uint32_t (&und)[3], uint32_t &board) const
+    {
+        const sdk_v4u *w = line(pos);
+        const sdk_v4u q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3], q4 = w[4], q5 = w[5], t = w[6], u = w[7];
+        PlaneStack::unpack(B, q0, q1, q2, q3, q4, q5, t);
+        und[0] = u.x; und[1] = u.y; und[2] = u.z;
+        board = u.w;
+        plane::pin_board(B);
+        return t.w;
+    }
+};
+
+struct ExactArgs {
+    const uint8_t *puzzles;
+    unsigned long long *count;
+    int32_t *status, *open;
+    uint64_t *head;
+    uint32_t *ring;
+    uint2 *park;
+    uint8_t *stack;
+    uint64_t n, cap, head0, limit, target;
+    uint32_t slot0, slice;
+};
+
+__device__ __forceinline__ uint64_t exact_first_lane(unsigned long long v)
+{
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+           __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+__global__ __launch_bounds__(EXACT_THREADS, EXACT_WAVES_PER_EU) void exact_kernel(const ExactArgs a)
+{
+    const int lane = threadIdx.x;
+    const PlaneStack stk = {__builtin_amdgcn_make_buffer_rsrc(a.stack + (size_t)blockIdx.x * EXACT_WAVE_BYTES, 0,
+                                                              (int)EXACT_WAVE_BYTES, 0x00020000),
+                            (uint32_t)lane * EXACT_LANE_BYTES};
+    const ExactShared sh = {a.head, a.ring, a.cap, a.head0, a.limit, a.target, a.slot0};
+    const uint32_t slice = a.slice;
+    uint2 *const mypark = a.park + (size_t)blockIdx.x * 64 + lane;
+    plane::Board B;
+    uint32_t und[3] = {0u, 0u, 0u}, nd[3] = {0u, 0u, 0u}, found = 0, passes = 0;
+    // a stack parked in the round before: the search goes on at its deepest level
+    const uint2 pk = *mypark;
+    uint32_t depth = pk.x, board = pk.y;
+    bool active = depth != 0, resume = active;
+    if (active) *mypark = make_uint2(0u, 0u);
+    int32_t dopen = 0;
+    uint32_t donated = 0, parks = 0;
+    bool tasks_out = false, boards_out = false;
+    for (;;) {
+        const bool want = !active && passes < slice;
+        const uint64_t wantm = __builtin_amdgcn_ballot_w64(want);
+        const int nwant = __builtin_popcountll(wantm);
+        const bool none_active = __builtin_amdgcn_ballot_w64(active) == 0;
+        const bool queue_out = tasks_out && boards_out;
+        if (none_active && (nwant == 0 || queue_out)) break;
+        if (!queue_out && nwant > 0 && (nwant >= plane::EXACT_REFILL || none_active)) {
+            uint64_t ntask = 0, tbase = 0, bbase = a.n;
+            if (!tasks_out) {
+                unsigned long long h = 0;
+                if (lane == 0)
+                    h = __hip_atomic_fetch_add(&a.head[plane::XH_CLAIM], (uint64_t)nwant, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                tbase = exact_first_lane(h);
+                const uint64_t len = a.limit - a.head0;
+                ntask = tbase >= len ? 0 : len - tbase < (uint64_t)nwant ? len - tbase : (uint64_t)nwant;
+                tasks_out = tbase + (uint64_t)nwant >= len;  // the readable part is handed out: no further claim
+            }
+            if (ntask < (uint64_t)nwant && !boards_out) {
+                const uint64_t k = (uint64_t)nwant - ntask;
+                unsigned long long h = 0;
+                if (lane == 0)
+                    h = __hip_atomic_fetch_add(&a.head[plane::XH_BOARDS], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                bbase = exact_first_lane(h);
+                boards_out = bbase + k >= a.n;
+            }
+            const uint64_t rank =
+                __builtin_amdgcn_mbcnt_hi((uint32_t)(wantm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wantm, 0u));
+            if (want && rank < ntask) {
+                // a task line: level 0 of this lane's stack, then as from a DEAD verdict
+                const uint32_t e = sh.get(a.head0 + tbase + rank, B, und, board);
+                stk.push(0, B, und, e);
+                depth = 1;
+                active = resume = true;
+            } else if (want && bbase + (rank - ntask) < a.n) {
+                board = (uint32_t)(bbase + (rank - ntask));
+                uint32_t x[21], given[3];
+                exact_load_words(a.puzzles + (size_t)board * 81, x);
+                bool clash = false;
+                if (!plane::load_words(B, x, clash, given)) {
+                    a.status[board] = SDK_INVALID;
+                    a.open[board] = 0;  // (the board's only task: nobody else touches its counter)
+                    dopen--;
+                } else if (clash) {
+                    a.open[board] = 0;  // no valid completion, an exact zero; rules B-D are unsound on such givens
+                    dopen--;
+                } else {
+                    active = true;
+                    resume = false;
+                    depth = 0;
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) {
+                        nd[b] = given[b];
+                        und[b] = plane::andn(plane::ROWS, given[b]);
+                    }
+                }
+            }
+        }
+        if (active) {
+            const int k = plane::exact_iter(B, und, nd, depth, found, passes, resume, slice, stk,
+                                            (uint32_t)plane::COUNT_MAX_DEPTH);
+            if (k != plane::X_CONT) {
+                active = false;
+                if (k == plane::X_FAULT) {
+                    a.status[board] = SDK_FAULT;
+                    found = 0;
+                }
+                if (found)
+                    __hip_atomic_fetch_add(&a.count[board], (unsigned long long)found, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                found = 0;
+                if (k != plane::X_STOP) {  // the task's end
+                    __hip_atomic_fetch_add(&a.open[board], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    dopen--;
+                } else if (plane::exact_donate(B, und, depth, board, stk, sh)) {
+                    if (depth > 1)
+                        __hip_atomic_fetch_add(&a.open[board], (int32_t)depth - 1, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+                    dopen += (int32_t)depth - 1;
+                    donated += depth;
+                } else {
+                    *mypark = make_uint2(depth, board);
+                    parks++;
+                }
+            }
+        }
+    }
+    // the wave's share of the call's counters: one atomic each
+    uint32_t most = passes;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        dopen += __shfl_xor(dopen, s, 64);
+        donated += __shfl_xor(donated, s, 64);
+        parks += __shfl_xor(parks, s, 64);
+        const uint32_t o = __shfl_xor(most, s, 64);
+        most = o > most ? o : most;
+    }
+    if (lane == 0) {
+        if (dopen)
+            __hip_atomic_fetch_add(&a.head[plane::XH_OPEN], (uint64_t)(int64_t)dopen, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        if (donated)
+            __hip_atomic_fetch_add(&a.head[plane::XH_DONATED], (uint64_t)donated, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        if (parks)
+            __hip_atomic_fetch_add(&a.head[plane::XH_PARKS], (uint64_t)parks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (most)
+            __hip_atomic_fetch_max(&a.head[plane::XH_MAXPASS], (uint64_t)most, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// a call's start: every board is one open task, nothing counted, nobody parked
+__global__ __launch_bounds__(256) void exact_init_kernel(unsigned long long *__restrict__ count,
+                                                          int32_t *__restrict__ status, int32_t *__restrict__ open,
+                                                          uint64_t n, uint2 *__restrict__ park, uint64_t lanes,
+                                                          uint64_t *__restrict__ head)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t i = t; i < n; i += stride) {
+        count[i] = 0;
+        status[i] = 0;
+        open[i] = 1;
+    }
+    for (uint64_t i = t; i < lanes; i += stride) park[i] = make_uint2(0u, 0u);
+    if (t < plane::XH_WORDS) head[t] = t == plane::XH_OPEN ? n : 0;
+}
+
+// a call's end: DONE / PARTIAL from the open-task counters; an INVALID or
+// FAULT status stays, with count 0 (never a partial number)
+__global__ __launch_bounds__(256) void exact_final_kernel(unsigned long long *__restrict__ count,
+                                                           int32_t *__restrict__ status,
+                                                           const int32_t *__restrict__ open, uint64_t n)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (status[i] == 0) status[i] = open[i] == 0 ? SDK_EXACT_DONE : SDK_EXACT_PARTIAL;
+        else count[i] = 0;
+    }
+}
+
+// ==================================================================== C ABI
+static std::atomic<int> g_exact_bpc{0};
+static std::mutex g_exact_mu;  // one launch sequence at a time
+
+// waves of a full grid on the current device: every CU at the kernel's occupancy
+static int64_t exact_full_waves()
+{
+    const int per_cu = 4 * EXACT_WAVES_PER_EU;  // four SIMDs per CU
+    return (int64_t)sdk_device_cu_count() * cached_occupancy(exact_kernel, EXACT_THREADS, per_cu, per_cu, g_exact_bpc);
+}
+
+// the grid of a call: the same in every round, whatever n (one heavy board
+// is spread over all of it)
+static int64_t exact_waves(int max_waves) { return max_waves > 0 ? (int64_t)max_waves : exact_full_waves(); }
+
+struct ExactLayout {
+    size_t stack, ring, park, open, bytes;
+    uint64_t waves, cap;
+};
+
+static ExactLayout exact_layout(int64_t n, int max_waves, int64_t max_tasks)
+{
+    ExactLayout l;
+    l.waves = (uint64_t)exact_waves(max_waves);
+    l.cap = plane::exact_ring_lines(64 * l.waves, (uint64_t)max_tasks);
+    l.stack = EXACT_HEAD_BYTES;
+    l.ring = l.stack + (size_t)l.waves * EXACT_WAVE_BYTES;
+    l.park = l.ring + (size_t)l.cap * 128;
+    l.open = l.park + (size_t)l.waves * 64 * 8;
+    l.bytes = l.open + (((size_t)n * 4 + 15) & ~(size_t)15);
+    return l;
+}
+
+extern "C" {
+
+size_t sdk_count_exact_scratch_bytes(int64_t n, int max_waves, int64_t max_tasks)
+{
+    if (n < 0 || n > EXACT_MAX_BOARDS || max_waves < 0 || max_tasks < 0 || max_tasks > EXACT_MAX_TASKS) return 0;
+    return exact_layout(n, max_waves, max_tasks).bytes;
+}
+
+int sdk_count_exact_batch(const uint8_t *d_boards, int64_t *d_count, int32_t *d_status, int64_t n, int slice,
+                          int max_rounds, int64_t max_tasks, void *d_scratch, size_t scratch_bytes, int max_waves,
+                          void *stream, int64_t *stats)
+{
+    if (n == 0) return 0;
+    if (n < 0 || n > EXACT_MAX_BOARDS || max_waves < 0 || slice < 1 || max_rounds < 1 || max_tasks < 0 ||
+        max_tasks > EXACT_MAX_TASKS)
+        return -2;
+    if (!d_boards || !d_count || ((uintptr_t)d_count & 7u) || !d_status || ((uintptr_t)d_status & 3u) || !d_scratch ||
+        ((uintptr_t)d_scratch & 15u))
+        return -2;
+    const ExactLayout l = exact_layout(n, max_waves, max_tasks);
+    if (scratch_bytes < l.bytes) return -2;
+    // every completion costs a pass: a pass budget below 2^63 keeps d_count from overflowing
+    if ((unsigned __int128)max_rounds * ((uint64_t)slice + plane::EXACT_RUN_MAX) * (64 * l.waves) >>  63) return -2;
+    std::lock_guard<std::mutex> lk(g_exact_mu);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t *sc = (uint8_t *)d_scratch;
+    ExactArgs a;
+    a.puzzles = d_boards;
+    a.count = (unsigned long long *)d_count;
+    a.status = d_status;
+    a.open = (int32_t *)(sc + l.open);
+    a.head = (uint64_t *)sc;
+    a.ring = (uint32_t *)(sc + l.ring);
+    a.park = (uint2 *)(sc + l.park);
+    a.stack = sc + l.stack;
+    a.n = (uint64_t)n;
+    a.cap = l.cap;
+    a.head0 = a.limit = 0;
+    a.target = plane::exact_fill_target(64 * l.waves, l.cap);
+    a.slot0 = 0;
+    a.slice = (uint32_t)slice;
+    const uint64_t most = (uint64_t)n > 64 * l.waves ? (uint64_t)n : 64 * l.waves;
+    const unsigned small = (unsigned)((most + 255) / 256 < 1024 ? (most + 255) / 256 : 1024);
+    hipLaunchKernelGGL(exact_init_kernel, dim3(small), dim3(256), 0, st, a.count, a.status, a.open, a.n, a.park,
+                       64 * l.waves, a.head);
+    if (hipGetLastError() != hipSuccess) return -1;
+    uint64_t h[8] = {0};
+    int rounds = 0;
+    for (;;) {
+        // the round's claim counter, re-armed in stream order before the kernel
+        if (rounds && hipMemsetAsync(&a.head[plane::XH_CLAIM], 0, 8, st) != hipSuccess) return -1;
+        hipLaunchKernelGGL(exact_kernel, dim3((unsigned)l.waves), dim3(EXACT_THREADS), 0, st, a);
+        if (hipGetLastError() != hipSuccess) return -1;
+        if (hipMemcpyAsync(h, a.head, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+        if (hipStreamSynchronize(st) != hipSuccess) return -1;
+        rounds++;
+        if (h[plane::XH_OPEN] == 0 || rounds >= max_rounds) break;
+        // lines claimed leave the queue; what the round appended joins it
+        const uint64_t len = a.limit - a.head0;
+        const uint64_t took = h[plane::XH_CLAIM] < len ? h[plane::XH_CLAIM] : len;
+        a.head0 += took;
+        a.slot0 = (uint32_t)((a.slot0 + took) % l.cap);
+        a.limit = h[plane::XH_TAIL];
+    }
+    const unsigned fin = (unsigned)(((uint64_t)n + 255) / 256 < 1024 ? ((uint64_t)n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(exact_final_kernel, dim3(fin), dim3(256), 0, st, a.count, a.status, a.open, a.n);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;
+    if (stats) {
+        stats[0] = rounds;
+        stats[1] = (int64_t)h[plane::XH_DONATED];
+        stats[2] = (int64_t)h[plane::XH_PARKS];
+        stats[3] = (int64_t)h[plane::XH_MAXPASS];
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -21,6 +21,11 @@ from . import _lib
 from ._lib import (SDK_CANCELLED, SDK_COUNT_MAX_LIMIT, SDK_INVALID, SDK_NO_RETURN, SDK_SOLVED, SDK_UNSOLVABLE,
                    SudokuHipError)
 
+# count_exact's defaults (chosen from scripts/exact_bench.py's sweep; at these the heaviest fixture
+# board needs 64 to 83 rounds and the empty board comes back PARTIAL after 6.4 s on one MI355X)
+EXACT_SLICE = 256
+EXACT_MAX_ROUNDS = 512
+
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
     "SDK_INVALID", "SDK_CANCELLED", "SDK_NO_RETURN", "SudokuHipError",
@@ -136,6 +141,7 @@ class BatchSolver:
         self._min_scratch = None  # minimize's scratch, likewise
         self._sample_scratch = None  # sample's scratch, likewise
         self._uniq_scratch = None  # unique_candidates' scratch, likewise
+        self._exact_scratch = None  # count_exact's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -236,6 +242,54 @@ class BatchSolver:
                                                     sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
         self._rc_only(rc, "sdk_count_solutions_batch")
         return (counts, first) if return_first else counts
+
+    # -------------------------------------------------------- exact count
+    def count_exact(self, boards, slice=None, max_rounds=None, max_tasks: int = 0, max_waves: int = 0, stream=None,
+                    return_status: bool = False, return_stats: bool = False):
+        """The exact number of completions of every board as an int64 (n,)
+        tensor, without a cap (sdk_count_exact_batch; library extension, no
+        reference counterpart).  A board's search tree is cut
+        into tasks on the GPU and shared over every lane, so one heavy board
+        uses the whole device.  Givens that repeat a digit in a unit count 0.
+        The call runs rounds of about `slice` passes a lane (default
+        EXACT_SLICE), at most max_rounds of them (default EXACT_MAX_ROUNDS); a
+        board still open then is SDK_EXACT_PARTIAL and its count a lower bound
+        (not reproducible).  Raises if any board is SDK_EXACT_PARTIAL or
+        SDK_FAULT, unless return_status asks for the int32 (n,) statuses: then
+        (counts, status) comes back and nothing is raised.  A byte > 9 counts
+        0 with status SDK_INVALID.  return_stats adds a dict (rounds, donated, parks,
+        max_passes) as the last element.  max_tasks: the capacity of each task
+        list (0: four tasks a lane); max_waves > 0 caps the grid; an exact
+        count never depends on any of the knobs.  SYNCHRONOUS on the stream;
+        one cached scratch tensor serves every call, ordered like the
+        workspace's."""
+        slice = EXACT_SLICE if slice is None else int(slice)
+        max_rounds = EXACT_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+        if slice < 1 or max_rounds < 1:
+            raise ValueError("slice and max_rounds must be >= 1")
+        if int(max_waves) < 0 or int(max_tasks) < 0:
+            raise ValueError("max_waves and max_tasks must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        counts = torch.empty(n, dtype=torch.int64, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = (ctypes.c_int64 * 4)()
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_exact_scratch",
+                               int(self.lib.sdk_count_exact_scratch_bytes(n, int(max_waves), int(max_tasks))))
+            rc = self.lib.sdk_count_exact_batch(p.data_ptr(), counts.data_ptr(), status.data_ptr(), n, slice, max_rounds,
+                                                int(max_tasks), sc.data_ptr(), sc.numel(), int(max_waves),
+                                                self._ws_stream(stream), st)
+        self._rc_only(rc, "sdk_count_exact_batch")
+        if not return_status and n:
+            bad = (status == _lib.SDK_EXACT_PARTIAL) | (status == _lib.SDK_FAULT)
+            if bool(bad.any().item()):
+                raise SudokuHipError(f"count_exact: {int(bad.sum().item())} of {n} boards without an exact count after "
+                                     f"{int(st[0])} rounds (return_status=True gives the statuses and lower bounds)")
+        out = (counts, status) if return_status else (counts,)
+        if return_stats:
+            out += (dict(zip(("rounds", "donated", "parks", "max_passes"), (int(v) for v in st))),)
+        return out[0] if len(out) == 1 else out
 
     # ---------------------------------------------------------- canonical
     def canonical(self, boards, return_sym: bool = False, return_autos: bool = False, slices: int = 0, stream=None):
