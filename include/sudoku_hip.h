@@ -17,9 +17,9 @@
  * passes it as an output too where that is allowed.  Aliasing an input with
  * an output is allowed only where an entry says so (sdk_solve_batch,
  * sdk_solve_batch_grid, sdk_solve_batches); every other entry needs its
- * arguments disjoint.  (sdk_count_solutions_batch reads the aligned dwords
- * that hold a board, so up to 3 bytes on either side of d_puzzles are read;
- * they never change an answer.)
+ * arguments disjoint.  (sdk_count_solutions_batch and sdk_count_exact_batch
+ * read the aligned dwords that hold a board, so up to 3 bytes on either side
+ * of the boards are read; they never change an answer.)
  *
  * Return codes: 0 = launched / ok, <0 = error (text in sdk_last_error()).
  *
@@ -617,7 +617,9 @@ int sdk_unique_candidates_batch(const uint8_t *d_boards, uint16_t *d_once /* n*8
  * no room), and the most passes any lane ran in one round.
  * d_count needs 8-byte alignment, d_status 4, d_boards none.  Inputs are never
  * modified, no byte outside these extents is written, and the arguments are
- * disjoint.
+ * disjoint.  Like the capped count, the call reads the aligned dwords that
+ * hold a board, so up to 3 bytes on either side of d_boards are read; they
+ * never change an answer.
  * d_scratch: at least sdk_count_exact_scratch_bytes(n, max_waves, max_tasks)
  * bytes of device memory, 16-byte aligned, contents irrelevant: the call arms
  * it itself on `stream`.  SINGLE-STREAM like a workspace; the solve workspace,

@@ -92,9 +92,7 @@ struct ExactShared {
     // the line of a position in [head0, head0 + cap)
     __device__ __forceinline__ sdk_v4u *line(uint64_t pos) const
     {
-        uint64_t s = (uint64_t)slot0 + (pos - head0);
-        if (s >= cap) s -= cap;
-        return (sdk_v4u *)(ring + s * plane::STACK_LINE_WORDS);
+        return (sdk_v4u *)(ring + plane::exact_slot(pos, head0, slot0, cap) * plane::STACK_LINE_WORDS);
     }
     __device__ __forceinline__ void put(uint64_t pos, plane::Board &B, const uint32_t (&und)[3], uint32_t entry,
                                         uint32_t board) const
@@ -395,11 +393,7 @@ int sdk_count_exact_batch(const uint8_t *d_boards, int64_t *d_count, int32_t *d_
         rounds++;
         if (h[plane::XH_OPEN] == 0 || rounds >= max_rounds) break;
         // lines claimed leave the queue; what the round appended joins it
-        const uint64_t len = a.limit - a.head0;
-        const uint64_t took = h[plane::XH_CLAIM] < len ? h[plane::XH_CLAIM] : len;
-        a.head0 += took;
-        a.slot0 = (uint32_t)((a.slot0 + took) % l.cap);
-        a.limit = h[plane::XH_TAIL];
+        plane::exact_advance(h[plane::XH_CLAIM], h[plane::XH_TAIL], l.cap, a.head0, a.slot0, a.limit);
     }
     const unsigned fin = (unsigned)(((uint64_t)n + 255) / 256 < 1024 ? ((uint64_t)n + 255) / 256 : 1024);
     hipLaunchKernelGGL(exact_final_kernel, dim3(fin), dim3(256), 0, st, a.count, a.status, a.open, a.n);

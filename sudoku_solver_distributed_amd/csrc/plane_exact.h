@@ -44,6 +44,8 @@
 // [limit, tail) is what this round appends, never read before the next
 // launch; an append of k lines needs tail + k - head0 <= cap, so no slot that
 // may still be read is written.  Tasks a round leaves unclaimed stay queued.
+// exact_slot maps a position to its line, exact_advance moves head0 and limit
+// on between rounds.
 //
 // Plain C++ for host and device: the kernel (exact_kernels.hip) and the host
 // model (tests/native/exact_host.cpp) run the same functions over their own
@@ -152,6 +154,29 @@ PS_FN uint64_t exact_fill_target(uint64_t lanes, uint64_t cap)
 PS_FN uint64_t exact_ring_lines(uint64_t lanes, uint64_t max_tasks)
 {
     return 2 * (max_tasks ? max_tasks : 4 * lanes);
+}
+
+// The ring's slot of a position in [head0, head0 + cap), slot0 being head0's
+// slot (head0 % cap, kept by exact_advance so that no lane divides): one
+// subtraction of cap at the most.
+PS_FN uint64_t exact_slot(uint64_t pos, uint64_t head0, uint32_t slot0, uint64_t cap)
+{
+    uint64_t s = (uint64_t)slot0 + (pos - head0);
+    if (s >= cap) s -= cap;
+    return s;
+}
+
+// Between two rounds, on the host: the lines claimed leave the queue (`claim`
+// is the round's XH_CLAIM, which may overshoot the queue's length), what the
+// round appended joins it (`tail` is its XH_TAIL).  Keeps head0 <= limit <=
+// tail <= head0 + cap and slot0 == head0 % cap.
+PS_FN void exact_advance(uint64_t claim, uint64_t tail, uint64_t cap, uint64_t &head0, uint32_t &slot0, uint64_t &limit)
+{
+    const uint64_t len = limit - head0;
+    const uint64_t took = claim < len ? claim : len;
+    head0 += took;
+    slot0 = (uint32_t)((slot0 + took) % cap);
+    limit = tail;
 }
 
 // idle lanes before a wave claims tasks (results never depend on it): the

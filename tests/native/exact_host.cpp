@@ -2,7 +2,9 @@
 // exact_kernel's lanes run) for the CPU test-suite (tests/test_exact_host.py):
 // W simulated waves of 64 lanes, stepped serially, wave after wave, round
 // after round, with the kernel's take / stop / donate / park / flush rules,
-// the same ring and the same counters.  Not a product path.
+// the same ring (plane::exact_slot, exact_advance, exact_reserve: the code that
+// ships) and the same counters; and exact_ring_sweep, which drives the ring's
+// arithmetic alone (tests/test_exact_props_host.py).  Not a product path.
 #include <vector>
 
 #include "../../sudoku_solver_distributed_amd/csrc/host_model.h"
@@ -28,12 +30,16 @@ struct Shared {
     uint64_t *head;
     uint32_t *ring;
     uint64_t cap, head0, limit, target;
+    uint32_t slot0;  // head0's slot
     bool wants() const { return head[plane::XH_TAIL] - limit < target; }
     uint64_t reserve(uint32_t k) const
     {
         return plane::exact_reserve(Atomics(), &head[plane::XH_TAIL], head0, cap, k);
     }
-    uint32_t *line(uint64_t pos) const { return ring + (pos % cap) * plane::STACK_LINE_WORDS; }
+    uint32_t *line(uint64_t pos) const
+    {
+        return ring + plane::exact_slot(pos, head0, slot0, cap) * plane::STACK_LINE_WORDS;
+    }
     void put(uint64_t pos, const plane::Board &B, const uint32_t (&und)[3], uint32_t entry, uint32_t board) const
     {
         uint32_t *w = line(pos);
@@ -88,10 +94,11 @@ extern "C" int exact_host_batch(const uint8_t *in, int64_t *count, int32_t *stat
         status[i] = 0;
     }
     uint64_t head0 = 0, limit = 0;
+    uint32_t slot0 = 0;
     int rounds = 0;
     while (rounds < max_rounds && head[plane::XH_OPEN] != 0) {
         head[plane::XH_CLAIM] = 0;
-        const Shared sh = {head, ring.data(), cap, head0, limit, plane::exact_fill_target(lanes, cap)};
+        const Shared sh = {head, ring.data(), cap, head0, limit, plane::exact_fill_target(lanes, cap), slot0};
         for (int w = 0; w < waves; ++w) {
             Lane L[64];
             int64_t dopen = 0;
@@ -200,9 +207,7 @@ extern "C" int exact_host_batch(const uint8_t *in, int64_t *count, int32_t *stat
             if (most > head[plane::XH_MAXPASS]) head[plane::XH_MAXPASS] = most;
         }
         rounds++;
-        const uint64_t len = limit - head0;
-        head0 += head[plane::XH_CLAIM] < len ? head[plane::XH_CLAIM] : len;
-        limit = head[plane::XH_TAIL];
+        plane::exact_advance(head[plane::XH_CLAIM], head[plane::XH_TAIL], cap, head0, slot0, limit);
     }
     for (int64_t i = 0; i < n; ++i) {
         if (status[i] == 0) status[i] = open[i] == 0 ? 1 : 2;
@@ -213,6 +218,58 @@ extern "C" int exact_host_batch(const uint8_t *in, int64_t *count, int32_t *stat
         stats[1] = (int64_t)head[plane::XH_DONATED];
         stats[2] = (int64_t)head[plane::XH_PARKS];
         stats[3] = (int64_t)head[plane::XH_MAXPASS];
+    }
+    return 0;
+}
+
+// The ring's arithmetic as it ships (plane::exact_slot, exact_advance,
+// exact_reserve), `rounds` seeded rounds for every cap in [cap_lo, cap_hi]:
+// a round claims a random number of lines (up to twice the queue's length, so
+// claims overshoot as the kernel's fetch-add does) and appends random runs of
+// 1..81 lines through exact_reserve until one finds no room or a random stop.
+// Checked every round: head0 <= limit <= tail <= head0 + cap; slot0 ==
+// head0 % cap; the slot of every position in [head0, head0 + cap) is pos %
+// cap; no position of [head0, limit) shares a slot with one of [limit, tail);
+// a reservation succeeds exactly when tail + k - head0 <= cap and returns the
+// old tail.  Returns 0, or 1000 * cap + the number of the check that failed.
+extern "C" int64_t exact_ring_sweep(uint64_t seed, int rounds, uint32_t cap_lo, uint32_t cap_hi)
+{
+    uint64_t x = seed;
+    auto rnd = [&x](uint64_t below) {  // splitmix64
+        x += 0x9E3779B97F4A7C15ull;
+        uint64_t z = x;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return (z ^ (z >> 31)) % below;
+    };
+    for (uint64_t cap = cap_lo; cap <= cap_hi; ++cap) {
+        uint64_t head0 = 0, limit = 0, tail = 0;
+        uint32_t slot0 = 0;
+        std::vector<int> used(cap);
+        for (int r = 0; r < rounds; ++r) {
+            // the round's appends
+            while (rnd(8) != 0) {
+                const uint32_t k = 1 + (uint32_t)rnd(rnd(4) ? (cap < 81 ? cap : 81) : 81);
+                const bool room = tail + k - head0 <= cap;
+                const uint64_t before = tail;
+                const uint64_t got = plane::exact_reserve(Atomics(), &tail, head0, cap, k);
+                if (got != (room ? before : plane::X_NO_ROOM) || tail != before + (room ? k : 0)) return 1000 * cap + 1;
+            }
+            if (!(head0 <= limit && limit <= tail && tail - head0 <= cap)) return 1000 * cap + 2;
+            if (slot0 != head0 % cap) return 1000 * cap + 3;
+            for (uint64_t pos = head0; pos < head0 + cap; ++pos)
+                if (plane::exact_slot(pos, head0, slot0, cap) != pos % cap) return 1000 * cap + 4;
+            std::fill(used.begin(), used.end(), 0);
+            for (uint64_t pos = head0; pos < limit; ++pos) used[plane::exact_slot(pos, head0, slot0, cap)]++;
+            for (uint64_t pos = limit; pos < tail; ++pos)
+                if (used[plane::exact_slot(pos, head0, slot0, cap)]++) return 1000 * cap + 5;
+            for (uint64_t s = 0; s < cap; ++s)
+                if (used[s] > 1) return 1000 * cap + 5;
+            // the round's claims, then the host's advance
+            const uint64_t len = limit - head0;
+            const uint64_t claim = rnd(4) ? rnd(2 * len + 2) : len + rnd(200);
+            plane::exact_advance(claim, tail, cap, head0, slot0, limit);
+        }
     }
     return 0;
 }
