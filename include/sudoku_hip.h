@@ -643,6 +643,76 @@ int sdk_count_exact_batch(const uint8_t *d_boards, int64_t *d_count /* n */, int
                           size_t scratch_bytes, int max_waves, void *stream,
                           int64_t *stats /* HOST, 4 values, NULL ok */);
 
+/* List every completion of n boards (library extension, no reference
+ * counterpart).  A completion is what
+ * sdk_count_solutions_batch counts: a valid grid that keeps the givens.  The
+ * search is sdk_count_exact_batch's, shared over every lane of the grid in
+ * rounds of fewer than slice + 82 passes a lane, with the same task ring and
+ * the same meaning of slice, max_rounds, max_tasks and max_waves; its leaves
+ * are the completions, each met once, and every one a lane meets and is
+ * allowed to list goes to ONE list shared by the whole call:
+ *   row k of d_grids = 81 bytes 1..9, d_owner[k] = the board it completes.
+ * Rows [0, listed) are all written, without holes; no byte at or beyond row
+ * `listed` is written.  The ORDER of the rows is unspecified and differs from
+ * run to run; the SET is reproducible: for a board with SDK_ENUM_DONE in a
+ * call that did not overflow, the set of its rows never depends on slice,
+ * max_tasks, max_waves, max_rounds, capacity, limit, the batch or the board's
+ * place in it.
+ * info (HOST memory, may be NULL) receives six values: rounds launched, task
+ * lines donated, lane parks, the most passes any lane ran in one round,
+ * `total` = the completions that asked for a row, `listed` = min(total,
+ * capacity).  When total > capacity the rows beyond the capacity are DROPPED
+ * (which ones is unspecified); they are still counted in d_count and the call
+ * still returns 0: the caller sees listed < total and may call again with
+ * capacity = total.  capacity == 0 is a pure count: d_count and d_status are
+ * sdk_count_exact_batch's (d_grids and d_owner may then be NULL).
+ *   d_status[i] == SDK_ENUM_DONE:    the search of board i ran out; d_count[i]
+ *       is its exact number of completions, and without an overflow all of
+ *       them are listed.  Givens that repeat a digit in a unit: 0, DONE.
+ *   d_status[i] == SDK_ENUM_LIMITED: only with limit > 0: board i has AT LEAST
+ *       `limit` completions; d_count[i] == limit, exactly `limit` distinct
+ *       completions of it asked for a row and the rest of its search was
+ *       dropped.  A board with exactly `limit` completions is LIMITED too
+ *       (ask for limit + 1 to tell).  The limit is strict: never more than
+ *       `limit` rows of one board ask for a row, so capacity >= n * limit
+ *       cannot overflow.  limit == 0: no limit.
+ *   d_status[i] == SDK_ENUM_PARTIAL: max_rounds ran out; d_count[i] is the
+ *       number of distinct completions met, all of which asked for a row: a
+ *       lower bound, not reproducible.
+ *   d_status[i] == SDK_INVALID:      a byte > 9; d_count[i] = 0, no row.
+ *   d_status[i] == SDK_FAULT:        a search outgrew its stack, which 81
+ *       levels make impossible; d_count[i] = 0; rows of that board already
+ *       listed may remain, to be discarded by status.
+ * SYNCHRONOUS on `stream` and thread-safe like sdk_count_exact_batch: the
+ * library runs one such launch sequence at a time.  d_count needs 8-byte
+ * alignment, d_status and d_owner 4, d_boards and d_grids none.  Inputs are
+ * never modified, no byte outside these extents is written, the arguments are
+ * disjoint, and up to 3 bytes on either side of d_boards are read without
+ * ever changing an answer.
+ * d_scratch: at least sdk_enumerate_scratch_bytes(n, max_waves, max_tasks)
+ * bytes of device memory, 16-byte aligned, contents irrelevant, SINGLE-STREAM.
+ * With W waves and T = max_tasks (or 256 W for 0) it holds exactly
+ *   256 + W * 64 * 81 * 128 + 2 T * 128 + W * 64 * 8 + 4 n rounded up to 16
+ * bytes, the exact count's layout.
+ * Returns 0 / -1 (HIP error) / -2 (bad arguments: those of
+ * sdk_count_exact_batch, and capacity < 0, capacity > 2^31 - 1, limit < 0,
+ * capacity > 0 with d_grids or d_owner NULL or d_owner misaligned), by return
+ * code only; arguments are checked before any launch and n == 0 returns 0
+ * before any other check.  sdk_enumerate_scratch_bytes returns 0 for bad
+ * arguments. */
+#define SDK_ENUM_DONE 1    /* the board's search ran out: d_count[i] is exact */
+#define SDK_ENUM_PARTIAL 2 /* the round budget ran out: d_count[i] is a lower bound */
+#define SDK_ENUM_LIMITED 3 /* the board has at least `limit` completions: d_count[i] == limit */
+size_t sdk_enumerate_scratch_bytes(int64_t n, int max_waves, int64_t max_tasks);
+int sdk_enumerate_batch(const uint8_t *d_boards, int64_t n,
+                        uint8_t *d_grids /* capacity*81, NULL ok iff capacity == 0 */,
+                        int32_t *d_owner /* capacity,    NULL ok iff capacity == 0 */,
+                        int64_t capacity, int64_t limit /* 0 = none */,
+                        int64_t *d_count /* n */, int32_t *d_status /* n */,
+                        int slice, int max_rounds, int64_t max_tasks,
+                        void *d_scratch, size_t scratch_bytes, int max_waves, void *stream,
+                        int64_t *info /* HOST, 6 values, NULL ok */);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -60,6 +60,8 @@ EXPORTS = (
     "sdk_unique_candidates_batch",
     "sdk_count_exact_scratch_bytes",
     "sdk_count_exact_batch",
+    "sdk_enumerate_scratch_bytes",
+    "sdk_enumerate_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -72,6 +74,10 @@ SDK_MIN_GREEDY = 0  # sdk_minimize_batch: erase givens turn by turn while one co
 SDK_MIN_PROBE = 1   # ... or test every given alone against the input board
 SDK_EXACT_DONE = 1     # sdk_count_exact_batch: the count is exact
 SDK_EXACT_PARTIAL = 2  # ... or a lower bound: the round budget ran out
+SDK_ENUM_DONE = 1     # sdk_enumerate_batch: the board's search ran out, its count is exact
+SDK_ENUM_PARTIAL = 2  # ... the round budget ran out: a lower bound
+SDK_ENUM_LIMITED = 3  # ... the board has at least `limit` completions
+SDK_ENUM_MAX_ROWS = 2 ** 31 - 1  # ... and the largest capacity of its list
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -163,6 +169,11 @@ def load() -> ctypes.CDLL:
     L.sdk_count_exact_scratch_bytes.argtypes = [i64, i32, i64]
     L.sdk_count_exact_batch.restype = i32
     L.sdk_count_exact_batch.argtypes = [vp, vp, vp, i64, i32, i32, i64, vp, sz, i32, vp, ctypes.POINTER(ctypes.c_int64)]
+    L.sdk_enumerate_scratch_bytes.restype = sz
+    L.sdk_enumerate_scratch_bytes.argtypes = [i64, i32, i64]
+    L.sdk_enumerate_batch.restype = i32
+    L.sdk_enumerate_batch.argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, i32, i32, i64, vp, sz, i32, vp,
+                                      ctypes.POINTER(ctypes.c_int64)]
     _lib = L
     return L
 

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(_HERE)
 # exact candidates, min_kernels.hip, the minimisation, and sample_kernels.hip,
 # the random completion, and uniq_kernels.hip, the unique candidates, units of
 # their own with the count's scheduler, DESIGN.md §15, §16, §17 and §18;
-# exact_kernels.hip, the exact count shared over the grid, likewise, §20)
+# exact_kernels.hip, the exact count shared over the grid, and enum_kernels.hip,
+# the completion list on the same rounds, likewise, §20 and §21)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -44,7 +45,8 @@ def sources(sched: str = _SCHED):
             ("min_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("sample_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
-            ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
+            ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
+            ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
 
 
 SRCS = sources()

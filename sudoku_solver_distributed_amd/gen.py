@@ -44,6 +44,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from ._lib import SudokuHipError
 from .solver import SDK_SOLVED, as_boards, get_solver
 from .sudoku import Sudoku
 
@@ -439,6 +440,75 @@ def class_ids(boards, device=None):
     first = torch.full((uniq.shape[0],), n, dtype=torch.int64, device=canon.device)
     first.scatter_reduce_(0, ids, torch.arange(n, dtype=torch.int64, device=canon.device), reduce="amin")
     return canon, ids, first
+
+
+# ------------------------------------------------------- completion lists
+_M64 = (1 << 64) - 1
+
+
+def _mix(x: int) -> int:
+    """sdk_sample_batch's mix (include/sudoku_hip.h), mod 2^64."""
+    x &= _M64
+    x ^= x >> 30
+    x = x * 0xBF58476D1CE4E5B9 & _M64
+    x ^= x >> 27
+    x = x * 0x94D049BB133111EB & _M64
+    return x ^ (x >> 31)
+
+
+def uniform_completions(boards, seed: int = 0, per_board: int = 1, first_key: int = 0, limit: int = 1 << 16,
+                        device=None):
+    """Uniform random completions: (grids (n * per_board, 81) uint8, status
+    (n * per_board,) int32), item q = i * per_board + j being a completion of
+    board i.  UNIFORM over the board's completions, where BatchSolver.sample
+    is explicitly not: the board's completions are listed
+    (BatchSolver.completions, sorted) and item q takes row
+    ((r >> 32) * count_i) >> 32 of board i's list, r = mix(mix(seed) +
+    first_key + q) mod 2^64 with sdk_sample_batch's mix -- a function of the
+    board, seed and key alone.  Only for boards whose completions fit the
+    list: a board with `limit` completions or more (SDK_ENUM_LIMITED) or one
+    left SDK_ENUM_PARTIAL raises SudokuHipError.  A board without a completion
+    gives status 0 and its own row, like sample; every other item status 1."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(boards, max_value=255))
+    n, per_board, limit = p.shape[0], int(per_board), int(limit)
+    if per_board < 1 or limit < 1:
+        raise ValueError("per_board and limit must be >= 1")
+    grids, offsets, count, status, info = solver.completions(p, limit=limit, return_status=True)
+    if info["listed"] < info["total"] or bool((status != 1).any().item()):
+        bad = int((status != 1).sum().item())
+        raise SudokuHipError(f"uniform_completions: {bad} of {n} boards without a complete list below "
+                                  f"limit={limit} (statuses {sorted(set(status.tolist()))})")
+    cnt, off = count.tolist(), offsets.tolist()
+    base = _mix(seed)
+    rows, st = [], []
+    for q in range(n * per_board):
+        i = q // per_board
+        r = _mix(base + int(first_key) + q)
+        st.append(1 if cnt[i] else 0)
+        rows.append(off[i] + (((r >> 32) * cnt[i]) >> 32) if cnt[i] else -1)
+    rows = torch.tensor(rows, dtype=torch.int64, device=p.device)
+    st = torch.tensor(st, dtype=torch.int32, device=p.device)
+    out = p.repeat_interleave(per_board, dim=0)
+    has = rows >= 0
+    out[has] = grids[rows[has]]
+    return out, st
+
+
+def completion_classes(board, limit: int = 0, capacity=None, device=None):
+    """How many essentially different grids a pattern of givens has:
+    (representatives (k, 81) uint8, multiplicities (k,) int64) -- the
+    canonical forms (BatchSolver.canonical) of the board's completions, each
+    once, in lexicographic order, and how many completions have each.
+    limit / capacity as in BatchSolver.completions, whose errors apply."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(board, max_value=255))
+    if p.shape[0] != 1:
+        raise ValueError("completion_classes takes one board")
+    grids, _ = solver.completions(p, limit=limit, capacity=capacity, sort=False)
+    if grids.shape[0] == 0:
+        return grids, torch.zeros(0, dtype=torch.int64, device=grids.device)
+    return torch.unique(solver.canonical(grids), dim=0, return_counts=True)
 
 
 # ------------------------------------------------------------ hard 17-clue set

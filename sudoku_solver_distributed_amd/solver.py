@@ -291,6 +291,88 @@ class BatchSolver:
             out += (dict(zip(("rounds", "donated", "parks", "max_passes"), (int(v) for v in st))),)
         return out[0] if len(out) == 1 else out
 
+    # -------------------------------------------------- completion list
+    def completions(self, boards, capacity=None, limit: int = 0, sort: bool = True, return_status: bool = False,
+                    slice=None, max_rounds=None, max_tasks: int = 0, max_waves: int = 0, stream=None):
+        """Every completion of every board (sdk_enumerate_batch; library
+        extension, no reference counterpart) in CSR form:
+        (grids (m, 81) uint8, offsets (n + 1,) int64), board i's completions
+        being grids[offsets[i]:offsets[i + 1]].  A completion is what
+        count_solutions counts; the search is count_exact's, shared over the
+        whole grid, with the same slice / max_rounds / max_tasks / max_waves.
+        sort=True (the default): rows ordered by board, then lexicographically
+        by their 81 bytes, so the result is reproducible bit for bit (torch
+        sorts on the device); sort=False only groups the rows by board, in an
+        order that differs from run to run.  limit > 0: at most `limit`
+        completions of a board are listed and the rest of its search is
+        dropped (status SDK_ENUM_LIMITED, which of them is unspecified).
+        capacity: rows of the list, default n * limit, or 2^20 without a
+        limit.  Without return_status an overflow raises SudokuHipError with
+        the number of rows needed in its message (retry with that capacity),
+        and so does a board left SDK_ENUM_PARTIAL or SDK_FAULT; with it,
+        (grids, offsets, count int64 (n,), status int32 (n,), info dict) come
+        back, grids holding only the rows actually listed (info["listed"] of
+        info["total"]) and rows of SDK_FAULT boards left out.  SYNCHRONOUS on
+        the stream; count_exact's cached scratch serves the call."""
+        slice = EXACT_SLICE if slice is None else int(slice)
+        max_rounds = EXACT_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+        limit = int(limit)
+        if slice < 1 or max_rounds < 1:
+            raise ValueError("slice and max_rounds must be >= 1")
+        if int(max_waves) < 0 or int(max_tasks) < 0 or limit < 0:
+            raise ValueError("max_waves, max_tasks and limit must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        capacity = (n * limit if limit else 1 << 20) if capacity is None else int(capacity)
+        if not 0 <= capacity <= _lib.SDK_ENUM_MAX_ROWS:
+            raise ValueError(f"capacity must be 0..{_lib.SDK_ENUM_MAX_ROWS}")
+        grids = torch.empty((capacity, 81), dtype=torch.uint8, device=self.device)
+        owner = torch.empty(capacity, dtype=torch.int32, device=self.device)
+        counts = torch.empty(n, dtype=torch.int64, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = (ctypes.c_int64 * 6)()
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_exact_scratch",
+                               int(self.lib.sdk_enumerate_scratch_bytes(n, int(max_waves), int(max_tasks))))
+            rc = self.lib.sdk_enumerate_batch(p.data_ptr(), n, grids.data_ptr() if capacity else None,
+                                              owner.data_ptr() if capacity else None, capacity, limit,
+                                              counts.data_ptr(), status.data_ptr(), slice, max_rounds, int(max_tasks),
+                                              sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream), st)
+        self._rc_only(rc, "sdk_enumerate_batch")
+        info = dict(zip(("rounds", "donated", "parks", "max_passes", "total", "listed"), (int(v) for v in st)))
+        if not return_status and n:
+            if info["listed"] < info["total"]:
+                raise SudokuHipError(f"completions: the list overflowed, {info['total']} rows asked for a slot and the "
+                                     f"capacity is {capacity} (call again with capacity={info['total']})")
+            bad = (status == _lib.SDK_ENUM_PARTIAL) | (status == _lib.SDK_FAULT)
+            if bool(bad.any().item()):
+                raise SudokuHipError(f"completions: {int(bad.sum().item())} of {n} boards without a complete list "
+                                     f"after {info['rounds']} rounds (return_status=True gives the statuses)")
+        m = info["listed"]
+        with torch.cuda.device(self.device):
+            g, o = grids[:m], owner[:m].to(torch.int64)
+            if n and m and bool((status == _lib.SDK_FAULT).any().item()):
+                keep = status[o] != _lib.SDK_FAULT
+                g, o = g[keep], o[keep]
+            order = None
+            if sort and g.shape[0] > 1:
+                # 81 digits of 4 bits in six int64 keys of 15 digits; stable sorts, the last key first
+                shifts = torch.arange(14, -1, -1, device=self.device, dtype=torch.int64) * 4
+                order = torch.arange(g.shape[0], device=self.device)
+                for k in range(5, -1, -1):
+                    part = g[:, 15 * k:15 * k + 15].to(torch.int64)
+                    key = (part << shifts[:part.shape[1]]).sum(dim=1)
+                    order = order[torch.sort(key[order], stable=True)[1]]
+            by = torch.sort(o if order is None else o[order], stable=True)[1]
+            order = by if order is None else order[by]
+            g = g[order].contiguous()
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            if n:
+                offsets[1:] = torch.cumsum(torch.bincount(o, minlength=n), dim=0)
+        if return_status:
+            return g, offsets, counts, status, info
+        return g, offsets
+
     # ---------------------------------------------------------- canonical
     def canonical(self, boards, return_sym: bool = False, return_autos: bool = False, slices: int = 0, stream=None):
         """The canonical (minlex) form of every board under Sudoku's
