@@ -522,12 +522,12 @@ PS_FN void pick_cell(const uint32_t und[3], int node_order, int &band, int &pos)
     }
 }
 
-// Fewest-candidates cell for the completion count (search mode M_COUNT
-// below): the first undetermined cell (band order, then bit order) with
-// exactly 2 candidates, else with exactly 3, else the first undetermined
-// cell.  Saturating candidate counters over the nine planes, per band.
-// the choice from the per-band masks of undetermined cells with exactly 2
-// (e2) and exactly 3 (e3) candidates (shared with the wave-wide solver)
+// Fewest-candidates cell of the analysis kernels' searches (plane_count.h,
+// plane_sample.h and what builds on them; the solve path's count mode used it
+// until pick_count_masks below): the first undetermined cell (band order,
+// then bit order) with exactly 2 candidates, else with exactly 3, else the
+// first undetermined cell -- the choice from the per-band masks of
+// undetermined cells with exactly 2 (e2) and exactly 3 (e3) candidates.
 //
 // SDK_PLANE_MRV_PICK 1 (round 5, off): among the two-candidate cells, one in
 // the column holding the most of them (lowest such column, first band) -- a
@@ -580,12 +580,48 @@ PS_FN void pick_mrv_masks(const uint32_t (&e2)[3], const uint32_t (&e3)[3], cons
     pos = __builtin_ctz(band == 0 ? w[0] : band == 1 ? w[1] : w[2]);
 }
 
-PS_FN void pick_mrv(const Board &B, const uint32_t und[3], int &band, int &pos)
+// The solve path's branch cell in M_COUNT (search_step_impl and the wave-wide
+// solver; every analysis kernel keeps pick_mrv_masks and its visiting order).
+// S = e2 if any band has a two-candidate cell, else e3 if any has a
+// three-candidate one, else und; the band with the fewest cells of S (and one
+// at least), ties to the band with the most undetermined cells, then to the
+// lowest band; the lowest cell of S there.  Few two-candidate cells in a band
+// mean a band near its fixpoint: a guess there settles it, where a guess in a
+// band full of them leaves most of them open (host study: 6.0 % fewer passes,
+// 14 % fewer branch nodes on the 17-clue corpus, scripts/pick_study.py,
+// DESIGN.md §3).  One key per band, (count - 1) * 32 + 27 - popcount(und):
+// a band without a cell of S wraps to the top of the range.
+// (Without the tie-break -- three v_bcnt_u32_b32 and 12 VALU fewer, 0.7 % more
+// passes -- the GPU rate was the same within its spread over 11 alternating
+// runs, profiles/r09; the tie-break keeps the fewer branch nodes.)
+// SDK_PLANE_COUNT_PICK: the function the two callers use -- the host study and
+// the tests' mutants declare a rule of their own before this header.
+#ifndef SDK_PLANE_COUNT_PICK
+#define SDK_PLANE_COUNT_PICK pick_count_masks
+#endif
+PS_FN void pick_count_masks(const uint32_t (&e2)[3], const uint32_t (&e3)[3], const uint32_t und[3], int &band,
+                            int &pos)
+{
+    const bool a2 = or3(e2[0], e2[1], e2[2]) != 0, a3 = or3(e3[0], e3[1], e3[2]) != 0;
+    uint32_t s[3], key[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        s[b] = a2 ? e2[b] : a3 ? e3[b] : und[b];
+        key[b] = ((uint32_t)__builtin_popcount(s[b]) - 1u) * 32u + (27u - (uint32_t)__builtin_popcount(und[b]));
+    }
+    band = key[1] < key[0] ? 1 : 0;
+    const uint32_t k01 = key[1] < key[0] ? key[1] : key[0];
+    band = key[2] < k01 ? 2 : band;
+    pos = __builtin_ctz(band == 0 ? s[0] : band == 1 ? s[1] : s[2]);
+}
+
+// per band, the undetermined cells with exactly 2 (e2) and exactly 3 (e3)
+// candidates
+PS_FN void cand_masks(const Board &B, const uint32_t und[3], uint32_t (&e2)[3], uint32_t (&e3)[3])
 {
     // per cell, the candidate count as bit-sliced binary s3 s2 s1 s0 from a
     // carry-save adder tree over the nine planes (full adder = one xor3 and
     // one maj3 bitop3): 19 ops per band where four saturating counters took 36
-    uint32_t e2[3], e3[3];
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
         const uint32_t *p = &B.P[0][b];
@@ -601,7 +637,20 @@ PS_FN void pick_mrv(const Board &B, const uint32_t und[3], int &band, int &pos)
         e2[b] = and_andn(und[b], s1, s0 | hi);                        // exactly 2
         e3[b] = and3(und[b], s1, s0) & ~hi;                           // exactly 3
     }
+}
+
+PS_FN void pick_mrv(const Board &B, const uint32_t und[3], int &band, int &pos)
+{
+    uint32_t e2[3], e3[3];
+    cand_masks(B, und, e2, e3);
     pick_mrv_masks(e2, e3, und, band, pos);
+}
+
+PS_FN void pick_count(const Board &B, const uint32_t und[3], int &band, int &pos)
+{
+    uint32_t e2[3], e3[3];
+    cand_masks(B, und, e2, e3);
+    SDK_PLANE_COUNT_PICK(e2, e3, und, band, pos);
 }
 
 PS_FN uint32_t band_word(const uint32_t (&w)[3], int band) { return band == 0 ? w[0] : band == 1 ? w[1] : w[2]; }
@@ -995,7 +1044,7 @@ PS_FN int search_step_impl(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], int 
             depth = 0;
             mst = mst_set_mode(mst, M_FINAL);
         } else {
-            if (mode == M_COUNT) pick_mrv(B, und, fix_band, fix_pos);
+            if (mode == M_COUNT) pick_count(B, und, fix_band, fix_pos);
             else pick_cell(und, node_order, fix_band, fix_pos);
             const uint32_t cand = cell_cand(B, fix_band, fix_pos);
             fix_d = cand & (0u - cand);

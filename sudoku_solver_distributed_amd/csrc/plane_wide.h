@@ -353,6 +353,19 @@ WD_FN void set_cell(V &w, const Lanes &L, int band, int pos, uint32_t dbit)
     w = pick(clr, andn(w, V(1u << pos)), w);
 }
 
+// the count mode's branch cell: plane::pick_count's choice from the same
+// planes, so a board handed over from the lane loop continues the same tree
+WD_FN void pick_count(const V &w, const V &und, const Lanes &L, int &band, int &pos)
+{
+    V t, th, f;
+    row_count234(pick(L.valid, w, V(0u)), t, th, f);
+    const V e2 = und & andn(t, th), e3 = und & andn(th, f);
+    const uint32_t u[3] = {rdl(und, 0), rdl(und, 16), rdl(und, 32)};
+    const uint32_t m2[3] = {rdl(e2, 0), rdl(e2, 16), rdl(e2, 32)};
+    const uint32_t m3[3] = {rdl(e3, 0), rdl(e3, 16), rdl(e3, 32)};
+    plane::SDK_PLANE_COUNT_PICK(m2, m3, u, band, pos);
+}
+
 enum { W_UNSOLVABLE = 0, W_SOLVED = 1, W_OVERFLOW = -1, W_CANCELLED = 2 };
 
 struct Stats {
@@ -421,12 +434,7 @@ WD_FN int solve(V &w, uint32_t &depth, const Stack &stk, const Lanes &L, int nod
             const uint32_t u[3] = {rdl(und, 0), rdl(und, 16), rdl(und, 32)};
             int band, pos;
             if (mode == plane::M_COUNT) {
-                V t, th, f;
-                row_count234(pick(L.valid, w, V(0u)), t, th, f);
-                const V e2 = und & andn(t, th), e3 = und & andn(th, f);
-                const uint32_t m2[3] = {rdl(e2, 0), rdl(e2, 16), rdl(e2, 32)};
-                const uint32_t m3[3] = {rdl(e3, 0), rdl(e3, 16), rdl(e3, 32)};
-                plane::pick_mrv_masks(m2, m3, u, band, pos);
+                pick_count(w, und, L, band, pos);
             } else {
                 plane::pick_cell(u, node_order, band, pos);
             }
