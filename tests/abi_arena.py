@@ -1,7 +1,9 @@
 """Caller memory for the C ABI's buffer contracts (test_abi_pool.py on the
-CPU, test_gpu_abi_buffers.py on the GPU): guarded arenas to carve the
-arguments from, and one pool of boards whose answers come from the oracle
-alone, built once per process and never modified.
+CPU, test_gpu_abi_buffers.py and test_gpu_abi_streams.py on the GPU): guarded
+arenas to carve the arguments from, one pool of boards whose answers come
+from the oracle alone, built once per process and never modified, and the
+harness of the poisoned-scratch and stream-order checks (_poisons,
+_on_side_stream).
 
 Arena: one uint8 buffer filled with one byte.  carve() hands out views at a
 chosen address mod 4 (byte arrays) or at their natural alignment (int32 /
@@ -224,3 +226,117 @@ def mixed(n, seed=0, kinds=KINDS):
     idx = np.concatenate([rng.permutation(src), rng.choice(src, size=max(0, n - len(src)))])[:n]
     rng.shuffle(idx)
     return idx
+
+
+# ------------------------------- poisoned scratch and stream order (the GPU)
+def _stream_handle(solver, stream=None):
+    s = stream if stream is not None else torch.cuda.current_stream(solver.device)
+    return int(s.cuda_stream)
+
+
+def _poisons(view):
+    """The two pre-fills of a scratch: 0xFF, then seeded random bytes."""
+    yield "0xFF", lambda: view.fill_(0xFF)
+    g = torch.Generator(device="cpu").manual_seed(view.numel())
+    yield "random", lambda: view.copy_(torch.randint(0, 256, (view.numel(),), dtype=torch.uint8, generator=g))
+
+
+@functools.lru_cache(maxsize=None)
+def _delay_rate(device):
+    """Units of device delay per millisecond: cycles of torch.cuda._sleep
+    where there is one, else fills of a 256 MB tensor (measured with events
+    on the device, after a warm-up)."""
+    big = None if hasattr(torch.cuda, "_sleep") else torch.empty(1 << 28, dtype=torch.uint8, device=device)
+
+    def run(units):
+        if big is None:
+            torch.cuda._sleep(int(units))
+        else:
+            for _ in range(int(units)):
+                big.fill_(1)
+    probe = 20_000_000 if big is None else 20
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(2):
+        torch.cuda.synchronize()
+        e0.record()
+        run(probe)
+        e1.record()
+        torch.cuda.synchronize()
+    return run, probe / e0.elapsed_time(e1)
+
+
+def _on_side_stream(solver, what, inputs, call, outputs, scratch=(), dirty=None, blocking=False):
+    """The library call on a side stream behind a delay and an input copy
+    queued on that stream only; the default stream stays idle.  inputs:
+    (argument view, device tensor with the real contents) pairs -- the views
+    hold 0xFF until the copy on the side stream runs; outputs: views, copied
+    on the side stream after the call; scratch: views the call fills for its
+    own later kernels, 0xFF before it; dirty: a call queued on the side
+    stream before the input copy that leaves the queue head used (the same
+    entry on the 0xFF inputs, into other outputs).  Returns the copies.  A
+    launch or memset on any other stream runs at once: it reads 0xFF, or its
+    result is overwritten (a queue head re-armed early is used again by
+    `dirty`), or never reaches the copy.
+
+    blocking: the entry is SYNCHRONOUS on its stream, so the host is back
+    from it only when the delay is long over.  `early` is then sampled after
+    the copies and fills are queued, immediately before the call; there is no
+    `dirty` call, and in its place the side stream carries, between the delay
+    and the call, the input copy, a refill of every output with OUT_FILL and
+    a refill of every scratch view with 0xFF: what an init kernel or a memset
+    wrote early on another stream is overwritten before the call's own
+    kernels start.  The outputs are read by the copies on the side stream
+    alone."""
+    assert not (blocking and dirty is not None)
+    run, rate = _delay_rate(solver.device)
+    side = torch.cuda.Stream(solver.device)
+    keep = [(v, v.clone()) for v in outputs]
+
+    def prepare():
+        if dirty is not None:
+            dirty(side)
+        for view, real in inputs:
+            view.copy_(real, non_blocking=True)
+        if blocking:
+            for v in outputs:
+                v.view(torch.uint8).fill_(OUT_FILL)
+            for v in scratch:
+                v.view(torch.uint8).fill_(IN_FILL)
+
+    # dry runs: every kernel loaded, then the host's time to enqueue what
+    # follows the delay, up to the call (the larger of two measurements); a
+    # blocking call's own time is no enqueue time, so it is left out and the
+    # call runs in the first dry run only
+    torch.cuda.synchronize()
+    enq_ms = 0.0
+    with torch.cuda.stream(side):
+        for k in range(3):
+            t0 = time.perf_counter()
+            prepare()
+            t1 = time.perf_counter()
+            if not (blocking and k):
+                call(side)
+            if k:
+                enq_ms = max(enq_ms, ((t1 if blocking else time.perf_counter()) - t0) * 1e3)
+            side.synchronize()
+    for view in [v for v, _ in inputs] + list(scratch):
+        view.view(torch.uint8).fill_(IN_FILL)
+    for v, was in keep:
+        v.copy_(was)
+    torch.cuda.synchronize()
+    delay_ms = 10.0 * enq_ms
+    after_delay = torch.cuda.Event()
+    with torch.cuda.stream(side):
+        run(max(1, delay_ms * rate))
+        after_delay.record(side)
+        prepare()
+        if blocking:
+            early = not after_delay.query()
+        call(side)
+        if not blocking:
+            early = not after_delay.query()
+        got = [v.clone() for v in outputs]
+    side.synchronize()
+    print(f"{what}: enqueue {enq_ms:.3f} ms, delay {delay_ms:.3f} ms")
+    assert early, f"{what}: the delay of {delay_ms:.3f} ms was over before the call was enqueued ({enq_ms:.3f} ms)"
+    return got

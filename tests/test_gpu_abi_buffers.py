@@ -13,10 +13,16 @@ Two comparisons are GPU against GPU, on top of those: canon's automorphism
 count and the peer node's state record against the wrapper's run on
 allocator-aligned tensors (the fixture has no counts; the record's layout is
 the library's own).  Ordered mode past the deferred list's capacity is not
-covered."""
+covered.
+
+Sections c and d here cover solve, check, first_candidate, peer_solve,
+expand_frontier, count_solutions and canonical.  The same two checks of the
+seven analysis entries -- rate, candidates, unique_candidates, minimize,
+sample, count_exact and enumerate -- are in test_gpu_abi_streams.py, on the
+harness both files share (abi_arena: _stream_handle, _poisons, _delay_rate,
+_on_side_stream)."""
 import ctypes
 import functools
-import time
 
 import numpy as np
 import pytest
@@ -25,7 +31,8 @@ import torch
 import abi_arena as A
 import count_cases as C
 import frontier_cases as F
-from abi_arena import IN_FILL, OUT_FILL, ORDERS, Arena
+from abi_arena import (IN_FILL, OUT_FILL, ORDERS, Arena, _delay_rate, _on_side_stream, _poisons,  # noqa: F401
+                       _stream_handle)
 from conftest import load_golden
 from oracle import oracle as O
 
@@ -39,11 +46,6 @@ COUNT_MARGIN = 1 << 20
 
 
 # ------------------------------------------------------------------ helpers
-def _stream_handle(solver, stream=None):
-    s = stream if stream is not None else torch.cuda.current_stream(solver.device)
-    return int(s.cuda_stream)
-
-
 def _kernel(solver, name):
     """Force a solve kernel; returns the selection to restore."""
     from sudoku_solver_distributed_amd import _lib
@@ -514,13 +516,6 @@ def test_guards_snapshot_stats(solver):
 
 
 # --------------------- c. exact-size, poisoned scratch and workspace
-def _poisons(view):
-    """The two pre-fills of a scratch: 0xFF, then seeded random bytes."""
-    yield "0xFF", lambda: view.fill_(0xFF)
-    g = torch.Generator(device="cpu").manual_seed(view.numel())
-    yield "random", lambda: view.copy_(torch.randint(0, 256, (view.numel(),), dtype=torch.uint8, generator=g))
-
-
 @pytest.mark.parametrize("n,max_waves", [(65, 0), (4097, 2), (4097, 0)])
 def test_exact_count_scratch(solver, n, max_waves):
     """Exactly sdk_count_scratch_bytes(n, max_waves) bytes inside guards,
@@ -618,83 +613,6 @@ def test_exact_workspace(solver):
 
 
 # ----------------------------------------------------------- d. stream order
-@functools.lru_cache(maxsize=None)
-def _delay_rate(device):
-    """Units of device delay per millisecond: cycles of torch.cuda._sleep
-    where there is one, else fills of a 256 MB tensor (measured with events
-    on the device, after a warm-up)."""
-    big = None if hasattr(torch.cuda, "_sleep") else torch.empty(1 << 28, dtype=torch.uint8, device=device)
-
-    def run(units):
-        if big is None:
-            torch.cuda._sleep(int(units))
-        else:
-            for _ in range(int(units)):
-                big.fill_(1)
-    probe = 20_000_000 if big is None else 20
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(2):
-        torch.cuda.synchronize()
-        e0.record()
-        run(probe)
-        e1.record()
-        torch.cuda.synchronize()
-    return run, probe / e0.elapsed_time(e1)
-
-
-def _on_side_stream(solver, what, inputs, call, outputs, scratch=(), dirty=None):
-    """The library call on a side stream behind a delay and an input copy
-    queued on that stream only; the default stream stays idle.  inputs:
-    (argument view, device tensor with the real contents) pairs -- the views
-    hold 0xFF until the copy on the side stream runs; outputs: views, copied
-    on the side stream after the call; scratch: views the call fills for its
-    own later kernels, 0xFF before it; dirty: a call queued on the side
-    stream before the input copy that leaves the queue head used (the same
-    entry on the 0xFF inputs, into other outputs).  Returns the copies.  A
-    launch or memset on any other stream runs at once: it reads 0xFF, or its
-    result is overwritten (a queue head re-armed early is used again by
-    `dirty`), or never reaches the copy."""
-    run, rate = _delay_rate(solver.device)
-    side = torch.cuda.Stream(solver.device)
-    keep = [(v, v.clone()) for v in outputs]
-
-    def enqueue():
-        if dirty is not None:
-            dirty(side)
-        for view, real in inputs:
-            view.copy_(real, non_blocking=True)
-        call(side)
-
-    # dry runs: every kernel loaded, then the host's time to enqueue what
-    # follows the delay, up to the call (the larger of two measurements)
-    torch.cuda.synchronize()
-    enq_ms = 0.0
-    with torch.cuda.stream(side):
-        for k in range(3):
-            t0 = time.perf_counter()
-            enqueue()
-            if k:
-                enq_ms = max(enq_ms, (time.perf_counter() - t0) * 1e3)
-            side.synchronize()
-    for view in [v for v, _ in inputs] + list(scratch):
-        view.view(torch.uint8).fill_(IN_FILL)
-    for v, was in keep:
-        v.copy_(was)
-    torch.cuda.synchronize()
-    delay_ms = 10.0 * enq_ms
-    after_delay = torch.cuda.Event()
-    with torch.cuda.stream(side):
-        run(max(1, delay_ms * rate))
-        after_delay.record(side)
-        enqueue()
-        early = not after_delay.query()
-        got = [v.clone() for v in outputs]
-    side.synchronize()
-    print(f"{what}: enqueue {enq_ms:.3f} ms, delay {delay_ms:.3f} ms")
-    assert early, f"{what}: the delay of {delay_ms:.3f} ms was over before the call was enqueued ({enq_ms:.3f} ms)"
-    return got
-
-
 def _dev(solver, array):
     return torch.from_numpy(np.array(array)).to(solver.device)
 
