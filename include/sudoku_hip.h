@@ -21,6 +21,13 @@
  * read the aligned dwords that hold a board, so up to 3 bytes on either side
  * of the boards are read; they never change an answer.)
  *
+ * Sizes: n is a count of rows, and every offset into an array is formed in 64
+ * bits.  Byte extents past 4 GiB are supported and tested (tests/
+ * test_gpu_large.py: boards, solutions and lists of 4.0 GiB at 53 025 065 rows,
+ * marks of 4.0 GiB at 26 512 921 rows); row indices up to 2^31 - 1.  Row
+ * indices beyond that, and int32 / int64 arrays of 2^31 bytes or more (2^29
+ * rows), are outside what the tests reach.
+ *
  * Return codes: 0 = launched / ok, <0 = error (text in sdk_last_error()).
  *
  * Each entry point replaces one reference interface
@@ -72,7 +79,10 @@ size_t sdk_workspace_bytes(void);
  * partly overlapping arrays are not allowed).
  * `ordered` != 0 selects frontier mode: once board i is solved, boards j > i
  * are abandoned (status SDK_CANCELLED) and the lowest solved index is kept in
- * the workspace (sdk_read_stats out[4]). */
+ * the workspace (sdk_read_stats out[4]).
+ * sdk_solve_batch, sdk_solve_batch_grid and sdk_solve_batches: byte extents
+ * past 4 GiB are supported and tested, out of place and in place, with either
+ * kernel; row indices up to 2^31 - 1. */
 int sdk_solve_batch(const uint8_t *d_puzzles, uint8_t *d_solutions, int32_t *d_status,
                     int64_t n, void *d_workspace, int order, int ordered, void *stream);
 
@@ -114,7 +124,8 @@ int sdk_solve_batches(const uint8_t *const *d_puzzles, uint8_t *const *d_solutio
 /* Batch Sudoku.check (mode 0, sudoku.py:119-140: every row, column and box
  * sums to 45 and holds 9 distinct values) or node.py's SudokuSolver.check
  * (mode 1, node.py:82-116: sums only).  d_ok[i] = 1/0.  d_ok must not alias
- * d_grids. */
+ * d_grids.  sdk_check_batch and sdk_first_candidate_batch: byte extents past
+ * 4 GiB are supported and tested; row indices up to 2^31 - 1. */
 int sdk_check_batch(const uint8_t *d_grids, int32_t *d_ok, int64_t n, int mode, void *stream);
 
 /* Batch of node.py "solve" tasks (node.py:384-406 -> 76-80,
@@ -135,7 +146,9 @@ int sdk_first_candidate_batch(const uint8_t *d_grids, const int32_t *d_cells,
  * node.py's `validations` counter after the call (one per
  * SudokuSolver.check: every is_valid_move plus the final check).
  * No two of the arrays may alias (d_out != d_boards), here and in
- * sdk_peer_solve_seq. */
+ * sdk_peer_solve_seq.  sdk_peer_solve_batch: byte extents past 2 GiB are
+ * supported and tested; row indices up to 2^31 - 1 (sdk_peer_solve_seq, one
+ * lane walking its requests in order, is not tested at such sizes). */
 int sdk_peer_solve_batch(const uint8_t *d_boards, uint8_t *d_out, int32_t *d_status, int32_t *d_validations,
                          int64_t n, void *stream);
 
@@ -169,7 +182,10 @@ int sdk_peer_solve_seq(const uint8_t *d_boards, uint8_t *d_out, int32_t *d_statu
  *   d_tmp:      scratch, n*81 bytes
  *   d_offsets:  n+1 int64; d_offsets[n] = total children (read it back)
  *   d_children: capacity cap*81 bytes; children past cap are not written.
- * Caller checks d_offsets[n] <= cap. */
+ * Caller checks d_offsets[n] <= cap.
+ * Byte extents past 4 GiB (nodes, children) are supported and tested, and so
+ * is a level of more than 2^26 nodes, which the library cuts into several
+ * launches; row indices up to 2^31 - 1. */
 int sdk_expand_frontier(const uint8_t *d_nodes, int64_t n, uint8_t *d_tmp, int64_t *d_offsets,
                         uint8_t *d_children, int64_t cap, int order, void *stream);
 
@@ -272,7 +288,10 @@ int sdk_set_plane_search(int mrv_after);
  * limit out of range, negative n or max_waves, a NULL pointer that is
  * required, scratch too small), by return code only (sdk_last_error() is not
  * set); arguments are checked before any launch and n == 0 returns 0.
- * sdk_count_scratch_bytes returns 0 for negative arguments. */
+ * sdk_count_scratch_bytes returns 0 for negative arguments; for every other n
+ * up to INT64_MAX it is exactly 256 + min(ceil(n / 64), waves) * 64 * 81 * 128.
+ * Byte extents past 4 GiB (puzzles, d_first) are supported and tested; row
+ * indices up to 2^31 - 1. */
 #define SDK_COUNT_MAX_LIMIT 1024
 size_t sdk_count_scratch_bytes(int64_t n, int max_waves);
 int sdk_count_solutions_batch(const uint8_t *d_puzzles, int32_t *d_count, uint8_t *d_first /* NULL ok */,
@@ -308,7 +327,10 @@ int sdk_count_solutions_batch(const uint8_t *d_puzzles, int32_t *d_count, uint8_
  * == d_boards, scratch too small), by return code only; arguments are
  * checked before any launch and n == 0 returns 0.
  * sdk_canonical_scratch_bytes returns 0 for negative or out-of-range
- * arguments. */
+ * arguments, and for an n whose 64 * n * slices bytes do not fit size_t (the
+ * batch entry refuses such an n).
+ * A scratch past 4 GiB (25 891 boards and more at 2592 slices) is supported and
+ * tested: the library cuts a batch into launches of fewer than 2^32 threads. */
 #define SDK_CANON_SYMMETRIES 3359232
 #define SDK_CANON_MAX_SLICES 2592
 size_t sdk_canonical_scratch_bytes(int64_t n, int slices);
@@ -359,7 +381,9 @@ int sdk_canonical_batch(const uint8_t *d_boards, uint8_t *d_canon, int32_t *d_sy
  * max_level out of range, n negative or above 2^31 - 1, a NULL pointer that
  * is required, a misaligned pointer, scratch too small), by return code only;
  * arguments are checked before any launch and n == 0 returns 0.
- * sdk_rate_scratch_bytes returns 0 for bad arguments. */
+ * sdk_rate_scratch_bytes returns 0 for bad arguments (n above 2^31 - 1 among
+ * them).  Byte extents past 4 GiB (d_marks) are supported and tested; row
+ * indices up to 2^31 - 1. */
 #define SDK_RATE_MAX_LEVEL 4
 #define SDK_RATE_NOT_RUN -2
 size_t sdk_rate_scratch_bytes(int64_t n, int max_level);
@@ -402,7 +426,9 @@ int sdk_rate_batch(const uint8_t *d_boards, int32_t *d_rating, int32_t *d_open /
  * negative n or max_waves, a NULL pointer that is required, a misaligned
  * pointer, scratch too small), by return code only (sdk_last_error() is not
  * set); arguments are checked before any launch and n == 0 returns 0.
- * sdk_candidates_scratch_bytes returns 0 for negative arguments. */
+ * sdk_candidates_scratch_bytes returns 0 for negative arguments.  Byte
+ * extents past 4 GiB (d_marks) are supported and tested; row indices up to
+ * 2^31 - 1. */
 size_t sdk_candidates_scratch_bytes(int64_t n, int max_waves);
 int sdk_candidates_batch(const uint8_t *d_boards, uint16_t *d_marks /* n*81 */, int32_t *d_count /* n, NULL ok */,
                          int64_t n, void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
@@ -448,7 +474,9 @@ int sdk_candidates_batch(const uint8_t *d_boards, uint16_t *d_marks /* n*81 */, 
  * that is required, a misaligned pointer, scratch too small, d_out ==
  * d_boards), by return code only (sdk_last_error() is not set); arguments are
  * checked before any launch and n == 0 returns 0 before any other check.
- * sdk_minimize_scratch_bytes returns 0 for negative arguments. */
+ * sdk_minimize_scratch_bytes returns 0 for negative arguments.  Byte extents
+ * past 4 GiB (d_boards, d_order, d_out) are supported and tested; row indices
+ * up to 2^31 - 1. */
 #define SDK_MIN_GREEDY 0
 #define SDK_MIN_PROBE 1
 size_t sdk_minimize_scratch_bytes(int64_t n, int max_waves);
@@ -515,7 +543,9 @@ int sdk_minimize_batch(const uint8_t *d_boards, const uint8_t *d_order /* n*81, 
  * d_boards, scratch too small), by return code only (sdk_last_error() is not
  * set); arguments are checked before any launch and n == 0 returns 0 before
  * any other check.  sdk_sample_scratch_bytes returns 0 for negative
- * arguments. */
+ * arguments.  Byte extents past 4 GiB (d_out) are supported and tested, with
+ * per_board > 1 and with keys that wrap past 2^64 inside the batch; item
+ * indices up to 2^31 - 1. */
 size_t sdk_sample_scratch_bytes(int64_t items, int max_waves);
 int sdk_sample_batch(const uint8_t *d_boards /* n*81, NULL = every board empty */, uint8_t *d_out /* items*81 */,
                      int32_t *d_status /* items */, int64_t n, int per_board, uint64_t seed, uint64_t first_key,
@@ -568,7 +598,9 @@ int sdk_sample_batch(const uint8_t *d_boards /* n*81, NULL = every board empty *
  * negative n or max_waves, a NULL pointer that is required, a misaligned
  * pointer, scratch too small), by return code only (sdk_last_error() is not
  * set); arguments are checked before any launch and n == 0 returns 0.
- * sdk_unique_candidates_scratch_bytes returns 0 for negative arguments. */
+ * sdk_unique_candidates_scratch_bytes returns 0 for negative arguments.  Byte
+ * extents past 4 GiB (d_once, d_marks) are supported and tested; row indices
+ * up to 2^31 - 1. */
 size_t sdk_unique_candidates_scratch_bytes(int64_t n, int max_waves);
 int sdk_unique_candidates_batch(const uint8_t *d_boards, uint16_t *d_once /* n*81 */,
                                 uint16_t *d_marks /* n*81, NULL ok */, int32_t *d_count /* n, NULL ok */,
@@ -634,7 +666,9 @@ int sdk_unique_candidates_batch(const uint8_t *d_boards, uint16_t *d_once /* n*8
  * pointer that is required, a misaligned pointer, scratch too small), by
  * return code only (sdk_last_error() is not set); arguments are checked
  * before any launch and n == 0 returns 0 before any other check.
- * sdk_count_exact_scratch_bytes returns 0 for bad arguments. */
+ * sdk_count_exact_scratch_bytes returns 0 for bad arguments (n above 2^31 - 1
+ * among them).  The entry has no array that reaches 2^31 bytes below 2^28
+ * boards and is not tested at such sizes. */
 #define SDK_EXACT_DONE 1    /* d_count[i] is the exact number of completions */
 #define SDK_EXACT_PARTIAL 2 /* the round budget ran out: d_count[i] is a lower bound */
 size_t sdk_count_exact_scratch_bytes(int64_t n, int max_waves, int64_t max_tasks);
@@ -699,7 +733,8 @@ int sdk_count_exact_batch(const uint8_t *d_boards, int64_t *d_count /* n */, int
  * capacity > 0 with d_grids or d_owner NULL or d_owner misaligned), by return
  * code only; arguments are checked before any launch and n == 0 returns 0
  * before any other check.  sdk_enumerate_scratch_bytes returns 0 for bad
- * arguments. */
+ * arguments (n above 2^31 - 1 among them).  A list past 4 GiB (d_grids: 54 M
+ * rows) is supported and tested; row indices up to 2^31 - 1. */
 #define SDK_ENUM_DONE 1    /* the board's search ran out: d_count[i] is exact */
 #define SDK_ENUM_PARTIAL 2 /* the round budget ran out: d_count[i] is a lower bound */
 #define SDK_ENUM_LIMITED 3 /* the board has at least `limit` completions: d_count[i] == limit */

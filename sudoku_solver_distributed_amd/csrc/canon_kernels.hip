@@ -40,7 +40,11 @@
 // lanes.  The queue holds what was left below that plus one round's 256.
 #define CANON_DRAIN_AT 22
 #define CANON_QUEUE (CANON_DRAIN_AT - 1 + CANON_THREADS)
-#define CANON_MAX_GRID 0x7FFFFFFFll
+// A launch's global size, workgroups times threads, is a 32-bit number: the runtime cuts a larger one to its
+// low 32 bits and runs that part of the grid without an error (25 898 boards at 2592 slices ran 16 384 of their
+// 67 M workgroups).  So a launch holds at most CANON_MAX_GRID workgroups of CANON_THREADS.
+#define CANON_MAX_GLOBAL 0xFFFFFFFFll
+#define CANON_MAX_GRID (CANON_MAX_GLOBAL / CANON_THREADS)
 
 // the workgroup's shared prefix
 struct LdsKey {
@@ -202,7 +206,9 @@ extern "C" {
 size_t sdk_canonical_scratch_bytes(int64_t n, int slices)
 {
     if (n < 0 || slices < 0 || slices > SDK_CANON_MAX_SLICES) return 0;
-    return (size_t)n * (size_t)canon_slices(n, slices) * (canon::RECORD_WORDS * sizeof(uint32_t));
+    const size_t per_board = (size_t)canon_slices(n, slices) * (canon::RECORD_WORDS * sizeof(uint32_t));
+    if (per_board && (size_t)n > SIZE_MAX / per_board) return 0;  // the size does not fit: no such batch
+    return (size_t)n * per_board;
 }
 
 int sdk_canonical_batch(const uint8_t *d_boards, uint8_t *d_canon, int32_t *d_sym, int32_t *d_autos, int64_t n,
@@ -210,11 +216,11 @@ int sdk_canonical_batch(const uint8_t *d_boards, uint8_t *d_canon, int32_t *d_sy
 {
     if (n < 0 || slices < 0 || slices > SDK_CANON_MAX_SLICES) return -2;
     if (n == 0) return 0;
-    if (!d_boards || !d_canon || !d_sym || !d_scratch || d_canon == d_boards ||
-        scratch_bytes < sdk_canonical_scratch_bytes(n, slices))
+    const size_t need = sdk_canonical_scratch_bytes(n, slices);  // 0: a size that does not fit size_t
+    if (!d_boards || !d_canon || !d_sym || !d_scratch || d_canon == d_boards || need == 0 || scratch_bytes < need)
         return -2;
     const int64_t rb = (n + CANON_REDUCE_THREADS - 1) / CANON_REDUCE_THREADS;
-    if (rb > CANON_MAX_GRID) return -2;
+    if (rb > CANON_MAX_GLOBAL / CANON_REDUCE_THREADS) return -2;
     hipStream_t st = (hipStream_t)stream;
     const int S = canon_slices(n, slices);
     // a launch's grid holds whole boards

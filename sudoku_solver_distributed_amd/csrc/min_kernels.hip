@@ -154,7 +154,7 @@ static int64_t min_full_waves()
 static int64_t min_waves(int64_t n, int max_waves)
 {
     const int64_t cap = max_waves > 0 ? (int64_t)max_waves : min_full_waves();
-    const int64_t want = (n + 63) / 64;
+    const int64_t want = n / 64 + (n % 64 != 0);  // (n + 63 would overflow at INT64_MAX)
     return want < cap ? want : cap;
 }
 

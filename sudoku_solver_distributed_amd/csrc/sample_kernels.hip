@@ -161,7 +161,7 @@ static int64_t sample_full_waves()
 static int64_t sample_waves(int64_t items, int max_waves)
 {
     const int64_t cap = max_waves > 0 ? (int64_t)max_waves : sample_full_waves();
-    const int64_t want = (items + 63) / 64;
+    const int64_t want = items / 64 + (items % 64 != 0);  // (items + 63 would overflow at INT64_MAX)
     return want < cap ? want : cap;
 }
 

@@ -750,13 +750,22 @@ int sdk_expand_frontier(const uint8_t *d_nodes, int64_t n, uint8_t *d_tmp, int64
         hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(int64_t), st);
         return e == hipSuccess ? 0 : set_err("sdk_expand_frontier: memset", e);
     }
-    const unsigned blocks = (unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+    // A launch's global size, workgroups times threads, is a 32-bit number: the runtime cuts a larger one to its low
+    // 32 bits and runs that part of the grid without an error.  At a wave a node that is 2^26 nodes, so the two
+    // node kernels take the nodes a slice a launch (one launch below that).
+    const int64_t per_launch = (0xFFFFFFFFll / BLOCK_THREADS) * WAVES_PER_BLOCK;
     // per-node child counts are written into d_offsets[0..n) and scanned in place
-    hipLaunchKernelGGL(expand_count_kernel, dim3(blocks), dim3(BLOCK_THREADS), 0, st, d_nodes, n, d_tmp, d_offsets,
-                       order);
+    for (int64_t first = 0; first < n; first += per_launch) {
+        const int64_t m = n - first < per_launch ? n - first : per_launch;
+        hipLaunchKernelGGL(expand_count_kernel, dim3((unsigned)((m + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)),
+                           dim3(BLOCK_THREADS), 0, st, d_nodes + first * 81, m, d_tmp + first * 81, d_offsets + first, order);
+    }
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, (const int64_t *)d_offsets, d_offsets, n);
-    hipLaunchKernelGGL(expand_write_kernel, dim3(blocks), dim3(BLOCK_THREADS), 0, st, d_tmp, n, d_offsets,
-                       d_children, cap, order);
+    for (int64_t first = 0; first < n; first += per_launch) {
+        const int64_t m = n - first < per_launch ? n - first : per_launch;
+        hipLaunchKernelGGL(expand_write_kernel, dim3((unsigned)((m + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)),
+                           dim3(BLOCK_THREADS), 0, st, d_tmp + first * 81, m, d_offsets + first, d_children, cap, order);
+    }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : set_err("sdk_expand_frontier: launch", e);
 }

@@ -158,6 +158,44 @@ def test_verify_workspace_arguments():
     assert L.sdk_verify_workspace(None, None, None) == -2
 
 
+def test_scratch_sizes_never_wrap():
+    """Every sdk_*_scratch_bytes at batch sizes up to INT64_MAX is the
+    header's formula in Python integers, or 0 where the header says the entry
+    does not take that n (rate, count_exact, enumerate: n above 2^31 - 1;
+    canonical: a size that does not fit size_t).  Host arithmetic only: no
+    batch entry is called, and every grid is given (max_waves, slices > 0), so
+    nothing asks for a device."""
+    from large_cases import N81
+    from sudoku_solver_distributed_amd import _lib
+    L = _lib.load()
+    sizes = (N81, 2 ** 31 - 1, 2 ** 31, 2 ** 40, 2 ** 62, 2 ** 63 - 1)
+    grids = (1, 7, 4096, 2 ** 31 - 1)
+    lane_queue = {"sdk_count_scratch_bytes": 81, "sdk_candidates_scratch_bytes": 83,
+                  "sdk_unique_candidates_scratch_bytes": 85, "sdk_minimize_scratch_bytes": 82,
+                  "sdk_sample_scratch_bytes": 81}  # stack lines a lane
+    for n in sizes:
+        for name, lines in lane_queue.items():
+            for waves in grids:
+                want = 256 + min(-(-n // 64), waves) * 64 * lines * 128
+                assert getattr(L, name)(n, waves) == want, (name, n, waves)
+        for level in (1, 2, 3, 4):
+            want = 0 if n > 2 ** 31 - 1 else 256 + (8 * n if level == 4 else 0)
+            assert L.sdk_rate_scratch_bytes(n, level) == want, (n, level)
+        for slices in (1, 2, 7, 36, _lib.SDK_CANON_MAX_SLICES):
+            want = 64 * n * slices
+            assert L.sdk_canonical_scratch_bytes(n, slices) == (want if want < 2 ** 64 else 0), (n, slices)
+        for name in ("sdk_count_exact_scratch_bytes", "sdk_enumerate_scratch_bytes"):
+            for waves in grids:
+                for tasks in (0, 1, 2 ** 31 - 1):
+                    t = tasks or 256 * waves
+                    want = 256 + waves * 64 * 81 * 128 + 2 * t * 128 + waves * 64 * 8 + (4 * n + 15) // 16 * 16
+                    assert getattr(L, name)(n, waves, tasks) == (0 if n > 2 ** 31 - 1 else want), (name, n, waves, tasks)
+    # the limits themselves, and what the header says of bad arguments
+    assert L.sdk_count_scratch_bytes(-1, 1) == 0 and L.sdk_rate_scratch_bytes(2 ** 31 - 1, 4) == 256 + 8 * (2 ** 31 - 1)
+    assert L.sdk_canonical_scratch_bytes(2 ** 58 - 1, 1) == 64 * (2 ** 58 - 1) and L.sdk_canonical_scratch_bytes(2 ** 58, 1) == 0
+    assert L.sdk_canonical_scratch_bytes(1, _lib.SDK_CANON_MAX_SLICES + 1) == 0
+
+
 def test_pipelined_launch_choice():
     """solve_inflight's SDK_GRID_PIPELINED choice (host logic): all but the
     last half of the launches in flight; none back to back; pool_last
