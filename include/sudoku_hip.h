@@ -748,6 +748,63 @@ int sdk_enumerate_batch(const uint8_t *d_boards, int64_t n,
                         void *d_scratch, size_t scratch_bytes, int max_waves, void *stream,
                         int64_t *info /* HOST, 6 values, NULL ok */);
 
+/* The smallest backdoors of n puzzles (library extension, no reference
+ * counterpart).  Item i is a board b (81 bytes 0..9) and a
+ * grid g (81 bytes 1..9) that is a valid Sudoku grid and keeps b's givens;
+ * the call has a level L in 1..SDK_BACKDOOR_MAX_LEVEL -- sdk_rate_batch's rule
+ * sets {N}, {N, H}, {N, H, L} -- and 1 <= max_size <= SDK_BACKDOOR_MAX_SIZE.
+ * For a set S of cells, b + S is b with b[c] = g[c] for c in S; S is a
+ * BACKDOOR when closure_L(b + S) is solved (it is then g: the rules are
+ * sound).  The rules are monotone, so every superset of a backdoor is one,
+ * and a minimum backdoor holds only cells that closure_L(b) leaves with two
+ * or more candidates.
+ *   d_size[i]           = the smallest |S| of a backdoor, 0..max_size (0
+ *                         exactly when sdk_rate_batch rates b 1..L at
+ *                         max_level L); max_size + 1 when no set of at most
+ *                         max_size cells is one; SDK_INVALID for a byte > 9
+ *                         in b or outside 1..9 in g; else
+ *                         SDK_BACKDOOR_MISMATCH when g is not a valid grid or
+ *                         does not keep b's givens;
+ *   d_count[i]          = how many backdoors have exactly that size (at most
+ *                         C(81, 4) = 1 663 740): 1 for size 0 (the empty
+ *                         set), 0 for max_size + 1 and the negative codes;
+ *   d_first[4 i .. + 3] = the lexicographically smallest backdoor of that
+ *                         size, cells ascending, 0xFF in the unused places;
+ *                         all 0xFF when there is none or the size is 0;
+ *   d_cover[81 i + c]   = 1 when cell c lies in at least one backdoor of that
+ *                         size, else 0.
+ * The answer depends on (b, g, L, max_size) alone: not on the grid size,
+ * max_waves, how the subsets are sliced, or the batch.  Size and count are
+ * the same for every symmetry image of (b, g) and the cover is the image of
+ * the cover; d_first is deterministic but NOT covariant (the smallest set of
+ * the image is not the image of the smallest set).  The size does not grow
+ * with L.  A board with several completions is legal: its backdoors are those
+ * that pin g.  d_count, d_first and d_cover may be NULL; d_size and d_count
+ * need 4-byte alignment, the byte arrays none.  Inputs are never modified and
+ * no byte outside these extents is written.
+ * d_scratch: at least sdk_backdoor_scratch_bytes(n, max_size, max_waves) bytes
+ * of device memory (256 + 320 n: a record for every board the level leaves
+ * open), 8-byte aligned, contents irrelevant: the call re-arms its counters
+ * itself on `stream`.  SINGLE-STREAM like a workspace; the solve workspace is
+ * not involved.  max_waves > 0 caps every kernel's grid (0: the device's
+ * waves at the kernel's occupancy); results never depend on it.
+ * Asynchronous on `stream`: one launch per size 1..max_size between a first
+ * and a last one, ordered by the stream alone.  Returns 0 / -1 (HIP error) /
+ * -2 (bad arguments: level or max_size out of range, n negative or above
+ * 2^31 - 1, max_waves negative, a NULL pointer that is required, a misaligned
+ * pointer, scratch too small), by return code only; arguments are checked
+ * before any launch and n == 0 returns 0.  sdk_backdoor_scratch_bytes returns
+ * 0 for bad arguments.  Row arithmetic is 64-bit throughout; byte extents
+ * past 4 GiB (d_boards, d_grids, d_cover: 53 M rows) are not yet tested. */
+#define SDK_BACKDOOR_MAX_LEVEL 3
+#define SDK_BACKDOOR_MAX_SIZE 4
+#define SDK_BACKDOOR_MISMATCH -2
+size_t sdk_backdoor_scratch_bytes(int64_t n, int max_size, int max_waves);
+int sdk_backdoor_batch(const uint8_t *d_boards, const uint8_t *d_grids, int32_t *d_size,
+                       int32_t *d_count /* n, NULL ok */, uint8_t *d_first /* n*4, NULL ok */,
+                       uint8_t *d_cover /* n*81, NULL ok */, int64_t n, int level, int max_size,
+                       void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -62,6 +62,8 @@ EXPORTS = (
     "sdk_count_exact_batch",
     "sdk_enumerate_scratch_bytes",
     "sdk_enumerate_batch",
+    "sdk_backdoor_scratch_bytes",
+    "sdk_backdoor_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -78,6 +80,9 @@ SDK_ENUM_DONE = 1     # sdk_enumerate_batch: the board's search ran out, its cou
 SDK_ENUM_PARTIAL = 2  # ... the round budget ran out: a lower bound
 SDK_ENUM_LIMITED = 3  # ... the board has at least `limit` completions
 SDK_ENUM_MAX_ROWS = 2 ** 31 - 1  # ... and the largest capacity of its list
+SDK_BACKDOOR_MAX_LEVEL = 3  # sdk_backdoor_batch: the deepest rule level of the closure
+SDK_BACKDOOR_MAX_SIZE = 4   # ... the largest subset tried
+SDK_BACKDOOR_MISMATCH = -2  # ... and the size of a grid that is not a completion of its board
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -174,6 +179,10 @@ def load() -> ctypes.CDLL:
     L.sdk_enumerate_batch.restype = i32
     L.sdk_enumerate_batch.argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, i32, i32, i64, vp, sz, i32, vp,
                                       ctypes.POINTER(ctypes.c_int64)]
+    L.sdk_backdoor_scratch_bytes.restype = sz
+    L.sdk_backdoor_scratch_bytes.argtypes = [i64, i32, i32]
+    L.sdk_backdoor_batch.restype = i32
+    L.sdk_backdoor_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -21,7 +21,9 @@ ROOT = os.path.dirname(_HERE)
 # the random completion, and uniq_kernels.hip, the unique candidates, units of
 # their own with the count's scheduler, DESIGN.md §15, §16, §17 and §18;
 # exact_kernels.hip, the exact count shared over the grid, and enum_kernels.hip,
-# the completion list on the same rounds, likewise, §20 and §21)
+# the completion list on the same rounds, likewise, §20 and §21;
+# backdoor_kernels.hip, the backdoor search on the rating's closures, a unit of
+# its own like rate_kernels.hip, LLVM's defaults, §23)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -46,7 +48,8 @@ def sources(sched: str = _SCHED):
             ("sample_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
-            ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]))
+            ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
+            ("backdoor_kernels.hip", []))
 
 
 SRCS = sources()

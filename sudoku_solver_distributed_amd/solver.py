@@ -9,6 +9,7 @@ Boards are ``uint8`` tensors of shape ``(n, 81)`` (row-major, 0 = empty).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -142,6 +143,7 @@ class BatchSolver:
         self._sample_scratch = None  # sample's scratch, likewise
         self._uniq_scratch = None  # unique_candidates' scratch, likewise
         self._exact_scratch = None  # count_exact's scratch, likewise
+        self._backdoor_scratch = None  # backdoors' scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -442,6 +444,80 @@ class BatchSolver:
         self._rc_only(rc, "sdk_rate_batch")
         out = (rating,) + ((opens,) if return_open else ()) + ((marks,) if return_marks else ())
         return out if len(out) > 1 else rating
+
+    # ---------------------------------------------------------- backdoors
+    def backdoors(self, boards, level: int = 2, max_size: int = 3, solutions=None, return_count: bool = False,
+                  return_first: bool = False, return_cover: bool = False, stream=None, max_waves: int = 0):
+        """The size of every puzzle's smallest backdoor, as an int32 (n,)
+        tensor (sdk_backdoor_batch; library extension, no reference
+        counterpart; the definition is in include/sudoku_hip.h and DESIGN.md
+        §23): the fewest cells which, filled with their digits of the
+        board's completion, let rate()'s rules of `level` (1 naked singles, 2
+        with hidden singles, 3 with locked candidates) finish the board; 0
+        exactly when rate(board, max_level=level) is 1..level; max_size + 1
+        when no set of at most max_size cells does (1 <= max_size <= 4).  It
+        grades the boards rate() leaves undecided and says where a board is
+        hard.  solutions: an (n, 81) tensor with the completion of every
+        board; a byte > 9 in a board or outside 1..9 in its completion gives
+        SDK_INVALID (-1), a completion that is no valid grid or does not keep
+        the givens SDK_BACKDOOR_MISMATCH (-2).  solutions=None: every board's
+        first completion from count_solutions(limit=2, return_first=True); a
+        board with no completion comes back as SDK_BACKDOOR_MISMATCH, and for
+        a board with several completions the backdoors are those to that
+        first one (the sets that pin it).  return_count: also an int32 (n,)
+        tensor, how many backdoors have that size (1 for size 0, 0 for
+        max_size + 1 and the negative codes); return_first: also a uint8
+        (n, 4) tensor, the lexicographically smallest of them, cells
+        ascending, 255 in unused places (deterministic, but not the image
+        under a symmetry); return_cover: also a uint8 (n, 81) tensor, 1 where
+        a cell lies in at least one of them.  Size, count and cover depend on
+        no search order, grid or batch.  max_waves > 0 caps the kernels'
+        grids; results never depend on it.  Asynchronous on the stream; one
+        cached scratch tensor serves every call, ordered like the
+        workspace's."""
+        level, max_size = int(level), int(max_size)
+        if not 1 <= level <= _lib.SDK_BACKDOOR_MAX_LEVEL:
+            raise ValueError(f"level must be 1..{_lib.SDK_BACKDOOR_MAX_LEVEL}")
+        if not 1 <= max_size <= _lib.SDK_BACKDOOR_MAX_SIZE:
+            raise ValueError(f"max_size must be 1..{_lib.SDK_BACKDOOR_MAX_SIZE}")
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        p = self._dev(as_boards(boards, max_value=255))
+        n = p.shape[0]
+        none = None  # the boards without a completion (solutions=None)
+        if solutions is None:
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                counts, g = self.count_solutions(p, limit=2, return_first=True, stream=stream, max_waves=max_waves)
+                none = counts == 0
+        else:
+            g = self._dev(as_boards(solutions, max_value=255))
+            if g.shape != p.shape:
+                raise ValueError("solutions must hold one grid per board")
+        size = torch.empty(n, dtype=torch.int32, device=self.device)
+        count = torch.empty(n, dtype=torch.int32, device=self.device) if return_count else None
+        first = torch.empty((n, 4), dtype=torch.uint8, device=self.device) if return_first else None
+        cover = torch.empty((n, 81), dtype=torch.uint8, device=self.device) if return_cover else None
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_backdoor_scratch", int(self.lib.sdk_backdoor_scratch_bytes(n, max_size, int(max_waves))))
+            rc = self.lib.sdk_backdoor_batch(p.data_ptr(), g.data_ptr(), size.data_ptr(),
+                                             count.data_ptr() if return_count else None,
+                                             first.data_ptr() if return_first else None,
+                                             cover.data_ptr() if return_cover else None, n, level, max_size,
+                                             sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
+        self._rc_only(rc, "sdk_backdoor_batch")
+        if none is not None:
+            # (the board itself stood in for the missing completion: whatever the kernels made of it)
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                size.masked_fill_(none, _lib.SDK_BACKDOOR_MISMATCH)
+                if return_count:
+                    count.masked_fill_(none, 0)
+                if return_first:
+                    first.masked_fill_(none[:, None], 255)
+                if return_cover:
+                    cover.masked_fill_(none[:, None], 0)
+        out = ((size,) + ((count,) if return_count else ()) + ((first,) if return_first else ())
+               + ((cover,) if return_cover else ()))
+        return out if len(out) > 1 else size
 
     # --------------------------------------------------------- candidates
     def candidates(self, boards, return_count: bool = False, stream=None, max_waves: int = 0):
