@@ -805,6 +805,69 @@ int sdk_backdoor_batch(const uint8_t *d_boards, const uint8_t *d_grids, int32_t 
                        uint8_t *d_cover /* n*81, NULL ok */, int64_t n, int level, int max_size,
                        void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
 
+/* The unavoidable sets of n solution grids (library extension, no reference
+ * counterpart).  Input i is a full grid g (81 bytes 1..9); the
+ * call has a size m = max_size, 4 <= m <= SDK_UA_MAX_SIZE.
+ *   A NEIGHBOUR of g is a valid grid g' != g; D(g') = {c : g'[c] != g[c]}.
+ *   Two cells c, c' of D are LINKED when they are peers (they share a row,
+ *   column or box) and g'[c] == g[c'] or g[c] == g'[c'].  A neighbour is
+ *   CONNECTED when D is connected under links.
+ *   A ROW is one connected neighbour with |D| <= m, as the 81-bit set D.  The
+ *   rows of g form a MULTISET: two neighbours with the same D give two rows.
+ * A neighbour that is not connected is a union of smaller connected ones, and
+ * every MINIMAL unavoidable set of at most m cells (a set inside which some
+ * neighbour differs from g, no proper subset of which is one) is the D of a
+ * row; the rows no other row's D is a proper subset of are exactly the minimal
+ * unavoidable sets of at most m cells (sdk_unavoidable_minimal_batch).
+ *   row k of d_rows = four words {m0, m1, m2, owner}: cell c is bit c & 31 of
+ *   word c >> 5, owner the grid's index.  One 16-byte store a row.
+ * Rows [0, listed) are all written, without holes; nothing at or beyond row
+ * `listed` is written.  The ORDER of the rows is unspecified and differs from
+ * run to run; the MULTISET is reproducible and depends on (g, m) alone.
+ *   d_info (DEVICE memory, 2 values) = {total, listed = min(total, capacity)};
+ *   when total > capacity the rows beyond the capacity are dropped (which ones
+ *   is unspecified) and the call still returns 0.  capacity == 0 is a pure
+ *   count (d_rows may then be NULL).
+ *   d_count[i]  = the rows of grid i, whatever the capacity;
+ *   d_status[i] = SDK_UA_DONE, or SDK_INVALID for a byte outside 1..9, else
+ *                 SDK_UA_NOT_A_GRID when a digit repeats in a row, column or
+ *                 box; the last two give count 0 and no row.
+ * d_rows needs 16-byte alignment, d_info 8, d_count and d_status 4, d_grids
+ * none.  Inputs are never modified and no byte outside these extents is
+ * written.
+ * d_scratch: at least sdk_unavoidable_scratch_bytes(n, max_waves) bytes of
+ * device memory (64 + 128 n: nine digit masks a grid), 8-byte aligned,
+ * contents irrelevant: the call re-arms its heads itself on `stream`.
+ * SINGLE-STREAM like a workspace; the solve workspace is not involved.
+ * max_waves > 0 caps every kernel's grid (0: the device's waves at the
+ * kernel's occupancy); results never depend on it.  Asynchronous on `stream`:
+ * three launches ordered by the stream alone.  Returns 0 / -1 (HIP error) /
+ * -2 (bad arguments: max_size out of range, n negative or above 2^31 - 1,
+ * capacity negative, max_waves negative, a NULL pointer that is required, a
+ * misaligned pointer, scratch too small), by return code only; arguments are
+ * checked before any launch and n == 0 returns 0.
+ * sdk_unavoidable_scratch_bytes returns 0 for bad arguments.  Row arithmetic
+ * is 64-bit throughout; a list past 4 GiB is not yet tested.
+ *
+ * sdk_unavoidable_minimal_batch: rows (four words each, the fourth ignored)
+ * already grouped in CSR form, group j the rows [d_offsets[j], d_offsets[j+1]).
+ *   d_keep[k] = 1 exactly when no row of k's group is a proper subset of row
+ *   k and no row of lower index in the group equals row k; else 0.
+ * No scratch; asynchronous on `stream`; d_rows needs 16-byte alignment,
+ * d_offsets 8.  Returns 0 / -1 / -2 (groups negative or above 2^31 - 1,
+ * max_waves negative, a NULL or misaligned pointer); groups == 0 returns 0. */
+#define SDK_UA_MAX_SIZE 16
+#define SDK_UA_DONE 1
+#define SDK_UA_NOT_A_GRID -2
+size_t sdk_unavoidable_scratch_bytes(int64_t n, int max_waves);
+int sdk_unavoidable_batch(const uint8_t *d_grids, int64_t n, int max_size,
+                          uint32_t *d_rows /* capacity*4, NULL ok iff capacity == 0 */, int64_t capacity,
+                          int32_t *d_count /* n */, int32_t *d_status /* n */,
+                          int64_t *d_info /* DEVICE, 2 values */,
+                          void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+int sdk_unavoidable_minimal_batch(const uint32_t *d_rows, const int64_t *d_offsets /* groups+1 */,
+                                  int64_t groups, uint8_t *d_keep, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -23,7 +23,8 @@ ROOT = os.path.dirname(_HERE)
 # exact_kernels.hip, the exact count shared over the grid, and enum_kernels.hip,
 # the completion list on the same rounds, likewise, §20 and §21;
 # backdoor_kernels.hip, the backdoor search on the rating's closures, a unit of
-# its own like rate_kernels.hip, LLVM's defaults, §23)
+# its own like rate_kernels.hip, LLVM's defaults, §23; ua_kernels.hip, the
+# unavoidable sets of a grid, likewise, §24)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -49,7 +50,8 @@ def sources(sched: str = _SCHED):
             ("uniq_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
-            ("backdoor_kernels.hip", []))
+            ("backdoor_kernels.hip", []),
+            ("ua_kernels.hip", []))
 
 
 SRCS = sources()

@@ -511,6 +511,61 @@ def completion_classes(board, limit: int = 0, capacity=None, device=None):
     return torch.unique(solver.canonical(grids), dim=0, return_counts=True)
 
 
+# ------------------------------------------------------------ unavoidable sets
+def _set_cells(sets: torch.Tensor) -> torch.Tensor:
+    """BatchSolver.unavoidable's sets, packed or not, as a bool (R, 81) tensor."""
+    if sets.dim() == 2 and sets.shape[1] == 3:
+        cells = torch.arange(81, device=sets.device)
+        return ((sets.to(torch.int64)[:, cells >> 5] >> (cells & 31)) & 1).bool()
+    if sets.dim() != 2 or sets.shape[1] != 81:
+        raise ValueError("sets must be (R, 81) or packed (R, 3)")
+    return sets.bool()
+
+
+def clue_lower_bound(grids, max_size: int = 12, device=None) -> torch.Tensor:
+    """A lower bound on the clues of every puzzle whose one solution is the
+    grid, as an int64 (n,) tensor: the size of a family of pairwise disjoint
+    minimal unavoidable sets of at most max_size cells
+    (BatchSolver.unavoidable) -- a puzzle needs a given in
+    each.  The family is GREEDY: the sets are taken in the listed order (by
+    size, then cell list), each one that meets none taken before.  Any
+    disjoint family is a valid bound; this is not the largest one (the clique
+    number of the disjointness graph), only a cheap one."""
+    solver = get_solver(device)
+    sets, offsets = solver.unavoidable(grids, max_size=max_size, minimal=True, packed=True)
+    n = offsets.shape[0] - 1
+    words = sets.to(torch.int64) & 0xFFFFFFFF
+    counts = offsets[1:] - offsets[:-1]
+    used = torch.zeros((n, 3), dtype=torch.int64, device=sets.device)
+    bound = torch.zeros(n, dtype=torch.int64, device=sets.device)
+    for r in range(int(counts.max().item()) if n else 0):
+        live = torch.nonzero(counts > r)[:, 0]
+        s = words[offsets[live] + r]
+        free = ((s & used[live]) == 0).all(dim=1)
+        live, s = live[free], s[free]
+        used[live] |= s
+        bound[live] += 1
+    return bound
+
+
+def hits_unavoidable(puzzles, sets, offsets, device=None) -> torch.Tensor:
+    """Per puzzle, whether its givens meet every listed unavoidable set of
+    its grid, as a bool (n,) tensor: (sets, offsets) as BatchSolver.unavoidable
+    returns them for the puzzles' solution grids, packed or not.  A puzzle
+    that misses one has a second completion -- the cheap necessary test before
+    any solver; with no set listed the answer is True."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(puzzles, max_value=255))
+    n = p.shape[0]
+    offsets = offsets.to(p.device)
+    if offsets.shape != (n + 1,):
+        raise ValueError("offsets must hold one entry per puzzle and one more")
+    cells = _set_cells(sets.to(p.device))
+    owner = torch.repeat_interleave(torch.arange(n, device=p.device), offsets[1:] - offsets[:-1])
+    missed = ~(cells & (p != 0)[owner]).any(dim=1)
+    return torch.zeros(n, dtype=torch.int64, device=p.device).index_add_(0, owner, missed.to(torch.int64)) == 0
+
+
 # ------------------------------------------------------------ hard 17-clue set
 def _perms(rng: np.random.Generator, shape, k: int) -> np.ndarray:
     """Uniform random permutations of range(k), vectorised over `shape`."""

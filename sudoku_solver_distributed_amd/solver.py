@@ -26,6 +26,11 @@ from ._lib import (SDK_CANCELLED, SDK_COUNT_MAX_LIMIT, SDK_INVALID, SDK_NO_RETUR
 # board needs 64 to 83 rounds and the empty board comes back PARTIAL after 6.4 s on one MI355X)
 EXACT_SLICE = 256
 EXACT_MAX_ROUNDS = 512
+# unavoidable's first capacity per grid, by max_size: twice the most rows any grid of tests/golden/ua_cases.json has
+# at that size (4..12, from its rows at 12); above 12, where the fixture records nothing, that figure grown 2.4 times
+# a cell, the growth DESIGN.md §24's table shows.  A guess only: a list that overflows is asked for again in full.
+UA_CAPACITY = {4: 32, 5: 32, 6: 162, 7: 162, 8: 170, 9: 330, 10: 578, 11: 1818, 12: 2070, 13: 4968, 14: 11923,
+               15: 28615, 16: 68676}
 
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
@@ -144,6 +149,7 @@ class BatchSolver:
         self._uniq_scratch = None  # unique_candidates' scratch, likewise
         self._exact_scratch = None  # count_exact's scratch, likewise
         self._backdoor_scratch = None  # backdoors' scratch, likewise
+        self._ua_scratch = None  # unavoidable's scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -444,6 +450,110 @@ class BatchSolver:
         self._rc_only(rc, "sdk_rate_batch")
         out = (rating,) + ((opens,) if return_open else ()) + ((marks,) if return_marks else ())
         return out if len(out) > 1 else rating
+
+    # ---------------------------------------------------- unavoidable sets
+    @staticmethod
+    def _rev32(x: torch.Tensor) -> torch.Tensor:
+        """Bit-reversal of 32-bit values held in int64."""
+        x = ((x >> 1) & 0x55555555) | ((x & 0x55555555) << 1)
+        x = ((x >> 2) & 0x33333333) | ((x & 0x33333333) << 2)
+        x = ((x >> 4) & 0x0F0F0F0F) | ((x & 0x0F0F0F0F) << 4)
+        x = ((x >> 8) & 0x00FF00FF) | ((x & 0x00FF00FF) << 8)
+        return ((x >> 16) & 0xFFFF) | ((x & 0xFFFF) << 16)
+
+    def unavoidable(self, grids, max_size: int = 12, minimal: bool = True, packed: bool = False, capacity=None,
+                    return_status: bool = False, stream=None, max_waves: int = 0):
+        """The unavoidable sets of every solution grid (sdk_unavoidable_batch
+        and sdk_unavoidable_minimal_batch; library extension, no reference
+        counterpart; the definitions are in include/sudoku_hip.h and DESIGN.md
+        §24) in CSR form: (sets, offsets (n + 1,) int64), grid i's sets being
+        sets[offsets[i]:offsets[i + 1]].  An unavoidable set of a grid g is a
+        set of cells inside which some other valid grid differs from g: every
+        puzzle with the one solution g has a given in each.  Listed are the
+        cell sets of the connected neighbours of at most max_size cells
+        (4 <= max_size <= SDK_UA_MAX_SIZE), each once; minimal=True (the
+        default) keeps those with no proper subset among them, which are
+        exactly the minimal unavoidable sets of at most max_size cells.  sets
+        is a uint8 (R, 81) 0/1 tensor, or with packed=True int32 (R, 3), cell
+        c bit c & 31 of word c >> 5.  Rows are ordered by grid, then size, then
+        their ascending cell lists compared lexicographically: the result is
+        reproducible bit for bit (torch sorts on the device).  capacity: rows
+        of the raw list; None starts from UA_CAPACITY[max_size] a grid and
+        asks once more with the exact number when that overflows, an explicit
+        one that overflows raises SudokuHipError with the number to ask for.
+        A grid with a byte outside 1..9 (SDK_INVALID) or a digit twice in a
+        unit (SDK_UA_NOT_A_GRID) raises, unless return_status asks for the
+        int32 (n,) statuses: then (sets, offsets, status) comes back and such
+        a grid has no set.  max_waves > 0 caps the kernels' grids; results
+        never depend on it.  SYNCHRONOUS on the stream (the list's length
+        comes back to the host); one cached scratch tensor serves every call,
+        ordered like the workspace's."""
+        max_size = int(max_size)
+        if not 4 <= max_size <= _lib.SDK_UA_MAX_SIZE:
+            raise ValueError(f"max_size must be 4..{_lib.SDK_UA_MAX_SIZE}")
+        if int(max_waves) < 0:
+            raise ValueError("max_waves must be >= 0")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        g = self._dev(as_boards(grids, max_value=255))
+        n = g.shape[0]
+        ctx = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        cap = n * UA_CAPACITY[max_size] if capacity is None else int(capacity)
+        with torch.cuda.device(self.device), ctx():
+            count = torch.empty(n, dtype=torch.int32, device=self.device)
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+            info = torch.zeros(2, dtype=torch.int64, device=self.device)
+            for attempt in range(2):
+                rows = torch.empty((cap, 4), dtype=torch.int32, device=self.device)
+                with self._lock:
+                    sc = self._scratch("_ua_scratch", int(self.lib.sdk_unavoidable_scratch_bytes(n, int(max_waves))))
+                    rc = self.lib.sdk_unavoidable_batch(g.data_ptr(), n, max_size, rows.data_ptr() if cap else None, cap,
+                                                        count.data_ptr(), status.data_ptr(), info.data_ptr(),
+                                                        sc.data_ptr(), sc.numel(), int(max_waves), self._ws_stream(stream))
+                self._rc_only(rc, "sdk_unavoidable_batch")
+                total, listed = (int(v) for v in info.tolist())
+                if listed == total:
+                    break
+                if capacity is not None:
+                    raise SudokuHipError(f"unavoidable: the list overflowed, {total} rows asked for a slot and the "
+                                         f"capacity is {cap} (call again with capacity={total})")
+                cap = total
+            if not return_status and n and bool((status != _lib.SDK_UA_DONE).any().item()):
+                raise SudokuHipError(f"unavoidable: {int((status != _lib.SDK_UA_DONE).sum().item())} of {n} inputs are "
+                                     f"no valid grids (return_status=True gives the statuses)")
+            # one sort for order and duplicates: rows of (grid, size, the three words bit-reversed and negated, so
+            # that the set holding the lowest cell two sets differ in comes first) compared lexicographically
+            w = rows[:listed].to(torch.int64) & 0xFFFFFFFF
+            size = torch.zeros(listed, dtype=torch.int64, device=self.device)
+            for k in range(3):
+                x = w[:, k]
+                x = x - ((x >> 1) & 0x55555555)
+                x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+                x = (x + (x >> 4)) & 0x0F0F0F0F
+                size += (x * 0x01010101 >> 24) & 0xFF
+            keys = torch.stack([w[:, 3], size] + [0xFFFFFFFF - self._rev32(w[:, k]) for k in range(3)], dim=1)
+            if listed:
+                keys = torch.unique(keys, dim=0)
+            owner = keys[:, 0]
+            words = torch.stack([self._rev32(0xFFFFFFFF - keys[:, 2 + k]) for k in range(3)], dim=1)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            if n:
+                offsets[1:] = torch.cumsum(torch.bincount(owner, minlength=n), dim=0)
+            if minimal and keys.shape[0]:
+                raw = torch.cat([words, owner[:, None]], dim=1).to(torch.int32).contiguous()
+                keep = torch.empty(raw.shape[0], dtype=torch.uint8, device=self.device)
+                rc = self.lib.sdk_unavoidable_minimal_batch(raw.data_ptr(), offsets.data_ptr(), n, keep.data_ptr(),
+                                                            int(max_waves), self._stream(stream))
+                self._rc_only(rc, "sdk_unavoidable_minimal_batch")
+                keep = keep.bool()
+                words, owner = words[keep], owner[keep]
+                offsets[1:] = torch.cumsum(torch.bincount(owner, minlength=n), dim=0)
+            if packed:
+                sets = words.to(torch.int32).contiguous()
+            else:
+                cells = torch.arange(81, device=self.device)
+                sets = ((words[:, cells >> 5] >> (cells & 31)) & 1).to(torch.uint8)
+        return (sets, offsets, status) if return_status else (sets, offsets)
 
     # ---------------------------------------------------------- backdoors
     def backdoors(self, boards, level: int = 2, max_size: int = 3, solutions=None, return_count: bool = False,
