@@ -868,6 +868,66 @@ int sdk_unavoidable_batch(const uint8_t *d_grids, int64_t n, int max_size,
 int sdk_unavoidable_minimal_batch(const uint32_t *d_rows, const int64_t *d_offsets /* groups+1 */,
                                   int64_t groups, uint8_t *d_keep, int max_waves, void *stream);
 
+/* The k-cell hitting sets of n families of cell sets (library extension, no
+ * reference counterpart).  Family i is the cell sets
+ * d_sets[d_offsets[i] .. d_offsets[i+1]) -- rows of four words {m0, m1, m2,
+ * ignored}, as sdk_unavoidable_batch writes them; only cells 0..80 of a set
+ * count -- an ALLOWED mask A = d_allowed[4 i ..] and a REQUIRED mask R =
+ * d_required[4 i ..] (three words and an ignored fourth each).  The call has a
+ * size k, 0 <= k <= SDK_HIT_MAX_CLUES.
+ *   A ROW of family i is a cell set S with R <= S <= A, |S| = k and
+ *   S & U != 0 for every set U of the family.
+ * The rows of a family form a SET, each S listed once; they depend on (the
+ * family's sets as a set of masks, A, R, k) alone, not on the order of the
+ * sets, on repeated sets or on max_waves.  So a set with no allowed cell that
+ * R does not hit (an all-zero mask among them) gives no row, an empty family
+ * gives every C(|A \ R|, k - |R|) filling, and k < |R| or k > |A| gives none.
+ *   row j of d_rows = four words {m0, m1, m2, owner}: cell c is bit c & 31 of
+ *   word c >> 5, owner the family's index.  One 16-byte store a row.
+ * Rows [0, listed) are all written, without holes; nothing at or beyond row
+ * `listed` is written.  The ORDER of the rows is unspecified.
+ *   d_info (DEVICE memory, 2 values) = {total, listed = min(total, capacity)};
+ *   when total > capacity the rows beyond the capacity are dropped (which ones
+ *   is unspecified) and the call still returns 0.  capacity == 0 is a count
+ *   (d_rows may then be NULL); with limit == 0 as well the search adds a
+ *   binomial where the clues left are free instead of walking the fillings.
+ *   A count that does not fit an int64 is unspecified.
+ *   limit > 0 stops a family after `limit` rows: d_count[i] == limit and the
+ *   status is SDK_HIT_LIMITED; which rows are listed is unspecified, each is a
+ *   row by the definition.  limit == 0: no limit.
+ *   d_count[i]  = the rows of family i, whatever the capacity;
+ *   d_status[i] = SDK_HIT_DONE, SDK_HIT_LIMITED, or SDK_INVALID when A or R
+ *                 has a bit at or above 81, R is not inside A, or the family's
+ *                 offsets descend or span 2^31 sets or more: count 0, no row.
+ * d_sets, d_allowed, d_required and d_rows need 16-byte alignment, d_offsets,
+ * d_count and d_info 8, d_status 4.  d_sets may be NULL when every family is
+ * empty.  Inputs are never modified and no byte outside these extents is
+ * written.
+ * d_scratch: at least sdk_hitting_sets_scratch_bytes(n, max_waves) bytes of
+ * device memory (64: the task head and the row cursor), 8-byte aligned,
+ * contents irrelevant: the call re-arms its heads itself on `stream`.
+ * SINGLE-STREAM like a workspace; the solve workspace is not involved.
+ * max_waves > 0 caps every kernel's grid (0: the device's waves at the
+ * kernel's occupancy); results never depend on it.  Asynchronous on `stream`:
+ * three launches ordered by the stream alone.  Returns 0 / -1 (HIP error) /
+ * -2 (bad arguments: k out of range, n negative or above 2^31 - 1, limit,
+ * capacity or max_waves negative, a NULL pointer that is required, a
+ * misaligned pointer, scratch too small), by return code only; arguments are
+ * checked before any launch and n == 0 returns 0.
+ * sdk_hitting_sets_scratch_bytes returns 0 for bad arguments.  Arithmetic is
+ * 64-bit throughout. */
+#define SDK_HIT_MAX_CLUES 32
+#define SDK_HIT_DONE 1
+#define SDK_HIT_LIMITED 2
+size_t sdk_hitting_sets_scratch_bytes(int64_t n, int max_waves);
+int sdk_hitting_sets_batch(const uint32_t *d_sets, const int64_t *d_offsets /* n+1 */,
+                           const uint32_t *d_allowed /* n*4 */, const uint32_t *d_required /* n*4 */,
+                           int64_t n, int k, int64_t limit,
+                           uint32_t *d_rows /* capacity*4, NULL ok iff capacity == 0 */, int64_t capacity,
+                           int64_t *d_count /* n */, int32_t *d_status /* n */,
+                           int64_t *d_info /* DEVICE, 2 values */,
+                           void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* Library / device info. */
 const char *sdk_last_error(void);
 const char *sdk_version(void);

@@ -67,6 +67,8 @@ EXPORTS = (
     "sdk_unavoidable_scratch_bytes",
     "sdk_unavoidable_batch",
     "sdk_unavoidable_minimal_batch",
+    "sdk_hitting_sets_scratch_bytes",
+    "sdk_hitting_sets_batch",
 )
 SDK_KERNELS = {"auto": 1, "packed": 5, "plane": 6}
 SDK_MAX_BATCHES = 32  # sdk_solve_batches: batches per launch
@@ -89,6 +91,9 @@ SDK_BACKDOOR_MISMATCH = -2  # ... and the size of a grid that is not a completio
 SDK_UA_MAX_SIZE = 16     # sdk_unavoidable_batch: the largest set listed
 SDK_UA_DONE = 1          # ... the status of a valid grid
 SDK_UA_NOT_A_GRID = -2   # ... and of one in which a digit repeats in a unit
+SDK_HIT_MAX_CLUES = 32   # sdk_hitting_sets_batch: the largest size k
+SDK_HIT_DONE = 1         # ... the status of a family that ran to the end
+SDK_HIT_LIMITED = 2      # ... and of one stopped at `limit` rows
 SDK_GRID_PIPELINED = 0x10000  # grid_waves flag: another launch is queued behind this one
 # device symbol of each solve kernel (rocprofv3 Kernel_Name, profiles/pmc_<symbol>.json)
 KERNEL_SYMBOLS = {1: "plane_kernel", 5: "solvep_kernel", 6: "plane_kernel"}
@@ -195,6 +200,10 @@ def load() -> ctypes.CDLL:
     L.sdk_unavoidable_batch.argtypes = [vp, i64, i32, vp, i64, vp, vp, vp, vp, sz, i32, vp]
     L.sdk_unavoidable_minimal_batch.restype = i32
     L.sdk_unavoidable_minimal_batch.argtypes = [vp, vp, i64, vp, i32, vp]
+    L.sdk_hitting_sets_scratch_bytes.restype = sz
+    L.sdk_hitting_sets_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_hitting_sets_batch.restype = i32
+    L.sdk_hitting_sets_batch.argtypes = [vp, vp, vp, vp, i64, i32, i64, vp, i64, vp, vp, vp, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -24,7 +24,8 @@ ROOT = os.path.dirname(_HERE)
 # the completion list on the same rounds, likewise, §20 and §21;
 # backdoor_kernels.hip, the backdoor search on the rating's closures, a unit of
 # its own like rate_kernels.hip, LLVM's defaults, §23; ua_kernels.hip, the
-# unavoidable sets of a grid, likewise, §24)
+# unavoidable sets of a grid, likewise, §24; hit_kernels.hip, the hitting
+# sets of a family of cell sets, likewise, §25)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -51,7 +52,8 @@ def sources(sched: str = _SCHED):
             ("exact_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("backdoor_kernels.hip", []),
-            ("ua_kernels.hip", []))
+            ("ua_kernels.hip", []),
+            ("hit_kernels.hip", []))
 
 
 SRCS = sources()

@@ -33,6 +33,11 @@
 * ``apply_symmetry(boards, sym)`` / ``class_ids(boards)`` -- the symmetry
   group in numbers and the isomorphism class of every board, by the GPU's
   canonical form (BatchSolver.canonical; library extension).
+* ``min_hitting_clues(grids)`` / ``smallest_sub_puzzles(puzzles)`` /
+  ``neighbourhood(puzzles, d)`` -- the hitting number of a grid's unavoidable
+  sets, the smallest proper puzzles inside a puzzle and the {-d, +d}
+  neighbours, by the GPU's hitting sets (BatchSolver.hitting_sets /
+  sub_puzzles; library extension).
 """
 from __future__ import annotations
 
@@ -532,7 +537,11 @@ def clue_lower_bound(grids, max_size: int = 12, device=None) -> torch.Tensor:
     disjoint family is a valid bound; this is not the largest one (the clique
     number of the disjointness graph), only a cheap one."""
     solver = get_solver(device)
-    sets, offsets = solver.unavoidable(grids, max_size=max_size, minimal=True, packed=True)
+    return _greedy_bound(*solver.unavoidable(grids, max_size=max_size, minimal=True, packed=True))
+
+
+def _greedy_bound(sets: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """clue_lower_bound on packed sets already listed."""
     n = offsets.shape[0] - 1
     words = sets.to(torch.int64) & 0xFFFFFFFF
     counts = offsets[1:] - offsets[:-1]
@@ -564,6 +573,151 @@ def hits_unavoidable(puzzles, sets, offsets, device=None) -> torch.Tensor:
     owner = torch.repeat_interleave(torch.arange(n, device=p.device), offsets[1:] - offsets[:-1])
     missed = ~(cells & (p != 0)[owner]).any(dim=1)
     return torch.zeros(n, dtype=torch.int64, device=p.device).index_add_(0, owner, missed.to(torch.int64)) == 0
+
+
+# ---------------------------------------------------------------- hitting sets
+def _take_families(sets: torch.Tensor, offsets: torch.Tensor, idx: torch.Tensor):
+    """The CSR lists of the families `idx` (with repeats, in that order)."""
+    lens = (offsets[1:] - offsets[:-1])[idx]
+    out = torch.zeros(idx.shape[0] + 1, dtype=torch.int64, device=offsets.device)
+    out[1:] = torch.cumsum(lens, dim=0)
+    rows = torch.repeat_interleave(offsets[idx] - out[:-1], lens) + torch.arange(int(out[-1].item()), device=offsets.device)
+    return sets[rows], out
+
+
+def min_hitting_clues(grids, max_size: int = 12, allowed=None, sets=None, device=None) -> torch.Tensor:
+    """SLOW on whole grids at the default max_size: every k below the answer
+    is searched to the end, which on all 81 cells with sets of 12 cells takes
+    one MI355X 51 s for a hard17 grid; max_size
+    8 or `allowed` cells make it milliseconds.
+
+    A PROVEN lower bound on the clues of every puzzle whose one solution is
+    the grid, as an int64 (n,) tensor: the least k for which some k cells meet
+    every minimal unavoidable set of at most max_size cells
+    (BatchSolver.unavoidable, BatchSolver.hitting_sets with limit=1; DESIGN.md
+    §25) -- the hitting number of that family.  The search runs upward from
+    clue_lower_bound's greedy packing, which it is never below: k clues cannot
+    meet more than k disjoint sets.  allowed (masks as in hitting_sets): the
+    bound for the puzzles whose clues lie inside those cells, never below the
+    unrestricted one and far cheaper to find.  sets: (sets, offsets) as
+    BatchSolver.unavoidable(grids, max_size, packed=True) returns them, when
+    the caller has them already."""
+    solver = get_solver(device)
+    sets, offsets = sets if sets is not None else solver.unavoidable(grids, max_size=max_size, minimal=True, packed=True)
+    if allowed is not None:
+        allowed = solver._cell_masks(allowed, offsets.shape[0] - 1, "allowed", 0)
+    n = offsets.shape[0] - 1
+    k_of = _greedy_bound(sets, offsets)
+    done = torch.zeros(n, dtype=torch.bool, device=sets.device)
+    k = int(k_of.min().item()) if n else 0
+    while n and not bool(done.all().item()):
+        if k > _lib_hit_max():
+            raise SudokuHipError(f"min_hitting_clues: no hitting set of {_lib_hit_max()} cells")
+        idx = torch.nonzero(~done & (k_of <= k))[:, 0]
+        if idx.shape[0]:
+            s, o = _take_families(sets, offsets, idx)
+            count = solver.hitting_sets(s, o, k, allowed=None if allowed is None else allowed[idx], limit=1, capacity=0,
+                                        return_count=True)[2]
+            done[idx[count > 0]] = True
+            k_of[idx[count == 0]] = k + 1
+        k += 1
+    return k_of
+
+
+def _lib_hit_max() -> int:
+    from ._lib import SDK_HIT_MAX_CLUES
+    return SDK_HIT_MAX_CLUES
+
+
+def smallest_sub_puzzles(puzzles, max_size: int = 12, device=None):
+    """The smallest proper puzzles inside proper puzzles: per puzzle the
+    least k at which some k of its givens still have one completion, and every
+    such sub-puzzle, as (k int64 (n,), sub-puzzles (R, 81) uint8, offsets
+    (n + 1,) int64).  The search runs upward from min_hitting_clues of the
+    solution grid inside the givens (below it no k givens meet the grid's
+    unavoidable sets) with BatchSolver.sub_puzzles(grid, k, allowed=givens).  A puzzle without
+    exactly one completion raises."""
+    solver = get_solver(device)
+    p = solver._dev(as_boards(puzzles))
+    n = p.shape[0]
+    counts, grids = solver.count_solutions(p, limit=2, return_first=True)
+    if n and bool((counts != 1).any().item()):
+        raise SudokuHipError(f"smallest_sub_puzzles: {int((counts != 1).sum().item())} of {n} puzzles are not proper")
+    sets = solver.unavoidable(grids, max_size=max_size, packed=True)
+    given = (p != 0).to(torch.uint8)
+    k_of = min_hitting_clues(grids, max_size=max_size, allowed=given, sets=sets, device=device)
+    clues = given.sum(dim=1).tolist()
+    done = torch.zeros(n, dtype=torch.bool, device=p.device)
+    found = [None] * n
+    k = int(k_of.min().item()) if n else 0
+    while n and not bool(done.all().item()):
+        idx = torch.nonzero(~done & (k_of <= k))[:, 0]
+        if idx.shape[0]:
+            if k > _lib_hit_max():
+                raise SudokuHipError(f"smallest_sub_puzzles: no sub-puzzle of {_lib_hit_max()} clues or fewer")
+            sub, off = solver.sub_puzzles(grids[idx], k, allowed=given[idx], sets=_take_families(sets[0], sets[1], idx))
+            off = off.tolist()
+            for j, i in enumerate(idx.tolist()):
+                if off[j + 1] > off[j] or k >= clues[i]:
+                    found[i] = sub[off[j]:off[j + 1]]
+                    done[i] = True
+                else:
+                    k_of[i] = k + 1
+        k += 1
+    per = torch.tensor([f.shape[0] for f in found], dtype=torch.int64, device=p.device)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=p.device)
+    offsets[1:] = torch.cumsum(per, dim=0)
+    subs = torch.cat(found) if n else torch.zeros((0, 81), dtype=torch.uint8, device=p.device)
+    return k_of, subs, offsets
+
+
+def neighbourhood(puzzles, d: int = 1, max_size: int = 12, device=None):
+    """The {-d, +d} neighbours of proper puzzles, d = 1..3: every proper
+    puzzle other than puzzle i itself that comes from it by erasing d clues
+    and adding d (a clue erased may come back, so the nearer neighbours are
+    among them), as (neighbours (m, 81) uint8, parent (m,) int64), each once a
+    parent, sorted by parent and then by ascending clue cells.  Every
+    neighbour has its parent's SOLUTION and number of clues: d = 1 gives the
+    boards of exchange() that complete to the parent's grid (exchange also
+    lists neighbours that complete to another grid; the unavoidable sets of
+    the parent's grid say nothing about those).  For every d-subset of the givens the rest is
+    `required` of one BatchSolver.sub_puzzles family of the solution grid at
+    k = the puzzle's clues.  Puzzles with no completion or several, or with a
+    byte > 9, contribute nothing.  One unavoidable call serves the batch; the
+    families are then built puzzle by puzzle, each d-subset with a copy of its
+    grid's sets (the CSR form has no way to share one list between families)."""
+    import itertools
+    if d not in (1, 2, 3):
+        raise ValueError("d must be 1, 2 or 3")
+    solver = get_solver(device)
+    p = solver._dev(as_boards(puzzles, max_value=255))
+    dev = p.device
+    counts, grids = solver.count_solutions(p, limit=2, return_first=True)
+    clues = (p != 0).sum(dim=1)
+    ok = (counts == 1) & (clues >= d) & (clues <= _lib_hit_max())
+    out, parents = [], []
+    live = torch.nonzero(ok)[:, 0]
+    usets, uoff = solver.unavoidable(grids[live], max_size=max_size, packed=True) if live.shape[0] else (None, None)
+    for at, i in enumerate(live.tolist()):
+        cells = torch.nonzero(p[i])[:, 0]
+        combos = torch.tensor(list(itertools.combinations(range(cells.shape[0]), d)), dtype=torch.int64, device=dev)
+        req = (p[i] != 0).to(torch.uint8).repeat(combos.shape[0], 1)
+        req[torch.arange(combos.shape[0], device=dev).unsqueeze(1), cells[combos]] = 0
+        fam = _take_families(usets, uoff, torch.full((combos.shape[0],), at, dtype=torch.int64, device=dev))
+        sub, _ = solver.sub_puzzles(grids[i:i + 1].expand(combos.shape[0], -1), int(clues[i]), required=req, sets=fam)
+        sub = torch.unique(sub, dim=0) if sub.shape[0] else sub
+        sub = sub[(sub != p[i]).any(dim=1)]
+        # torch.unique orders boards by digits; the public order is by clue cells: the board with a clue in the first
+        # cell two differ in comes first (three keys of 27 cells, cell 0 the highest bit, each descending)
+        weight = 1 << (26 - torch.arange(81, device=dev) % 27)
+        for j in (2, 1, 0):
+            key = ((sub[:, 27 * j:27 * j + 27] != 0) * weight[27 * j:27 * j + 27]).sum(dim=1)
+            sub = sub[torch.sort(key, descending=True, stable=True)[1]]
+        out.append(sub)
+        parents.append(torch.full((sub.shape[0],), i, dtype=torch.int64, device=dev))
+    if not out:
+        return torch.zeros((0, 81), dtype=torch.uint8, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+    return torch.cat(out), torch.cat(parents)
 
 
 # ------------------------------------------------------------ hard 17-clue set

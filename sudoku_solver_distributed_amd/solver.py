@@ -31,6 +31,10 @@ EXACT_MAX_ROUNDS = 512
 # a cell, the growth DESIGN.md §24's table shows.  A guess only: a list that overflows is asked for again in full.
 UA_CAPACITY = {4: 32, 5: 32, 6: 162, 7: 162, 8: 170, 9: 330, 10: 578, 11: 1818, 12: 2070, 13: 4968, 14: 11923,
                15: 28615, 16: 68676}
+# hitting_sets' first capacity in rows (16 bytes each); a list that overflows is asked for again in full
+HIT_CAPACITY = 1 << 16
+# the most candidates of one grid sub_puzzles lists (4 GiB of packed rows); more raises instead of an allocation failure
+SUB_PUZZLES_MAX_ROWS = 1 << 28
 
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
@@ -150,6 +154,7 @@ class BatchSolver:
         self._exact_scratch = None  # count_exact's scratch, likewise
         self._backdoor_scratch = None  # backdoors' scratch, likewise
         self._ua_scratch = None  # unavoidable's scratch, likewise
+        self._hit_scratch = None  # hitting_sets' scratch, likewise
         with torch.cuda.device(self.device):
             self.workspace = torch.zeros(int(self.lib.sdk_workspace_bytes()), dtype=torch.uint8,
                                          device=self.device)
@@ -554,6 +559,177 @@ class BatchSolver:
                 cells = torch.arange(81, device=self.device)
                 sets = ((words[:, cells >> 5] >> (cells & 31)) & 1).to(torch.uint8)
         return (sets, offsets, status) if return_status else (sets, offsets)
+
+    # -------------------------------------------------------- hitting sets
+    def _cell_masks(self, x, n: int, what: str, default: int) -> torch.Tensor:
+        """An allowed / required argument as the C ABI's (n, 4) int32 words:
+        None (every family `default`, an 81-bit int), one mask for all or one
+        a family, as (81,) / (n, 81) 0/1 values or packed (3 or 4 words)."""
+        if x is None:
+            x = torch.tensor([default & 0xFFFFFFFF, (default >> 32) & 0xFFFFFFFF, default >> 64], dtype=torch.int64)
+        x = self._dev(torch.as_tensor(x))
+        if x.dim() == 1:
+            x = x.unsqueeze(0).expand(n, -1)
+        if x.dim() != 2 or x.shape[0] != n or x.shape[1] not in (81, 3, 4):
+            raise ValueError(f"{what} must be (n, 81) cells or packed (n, 3) words, or one row for every family")
+        if x.shape[1] == 81:
+            cells = torch.arange(81, device=self.device)
+            bits = (x != 0).to(torch.int64) << (cells & 31)
+            x = torch.stack([bits[:, (cells >> 5) == w].sum(dim=1) for w in range(3)], dim=1)
+        x = x.to(torch.int64) & 0xFFFFFFFF
+        out = torch.zeros((n, 4), dtype=torch.int64, device=self.device)
+        out[:, :3] = x[:, :3]
+        return (out - ((out >> 31) << 32)).to(torch.int32).contiguous()
+
+    def hitting_sets(self, sets, offsets, k: int, allowed=None, required=None, limit: int = 0, packed: bool = False,
+                     capacity=None, return_status: bool = False, return_count: bool = False, stream=None,
+                     max_waves: int = 0):
+        """The k-cell hitting sets of every family of cell sets
+        (sdk_hitting_sets_batch; library extension, no reference counterpart;
+        the definitions are in include/sudoku_hip.h and DESIGN.md §25) in CSR
+        form: (rows, offsets (n + 1,) int64).  Family i is
+        sets[offsets[i]:offsets[i + 1]] -- (S, 81) 0/1 or packed (S, 3) / (S,
+        4) words, both forms BatchSolver.unavoidable returns -- with allowed[i]
+        (None: all 81 cells) and required[i] (None: no cell), each (n, 81),
+        packed (n, 3), or one row for all families.  A row is a set S of
+        exactly k cells (0 <= k <= SDK_HIT_MAX_CLUES) with required <= S <=
+        allowed that meets every set of the family; each is listed once,
+        whatever the order of the sets or their repeats.  rows is a uint8 (R,
+        81) 0/1 tensor, or with packed=True int32 (R, 3); ordered by family,
+        then by their ascending cell lists compared lexicographically.
+        limit > 0 stops a family after that many rows (which ones is
+        unspecified).  capacity: rows of the raw list; None starts from
+        HIT_CAPACITY and asks once more with the exact number when that
+        overflows, an explicit one that overflows raises SudokuHipError with
+        the number to ask for, except capacity=0, which lists nothing: with
+        return_count -- the int64 (n,) rows of every family as a further value
+        -- and limit=0 that is a pure count, which never walks free fillings.
+        A family whose masks have a bit at or above 81, or required outside
+        allowed (SDK_INVALID), raises, unless return_status asks for the int32
+        (n,) statuses (SDK_HIT_DONE, SDK_HIT_LIMITED, SDK_INVALID) as a third
+        value.  max_waves > 0 caps
+        the kernels' grids; results never depend on it.  SYNCHRONOUS on the
+        stream; one cached scratch tensor serves every call."""
+        k, limit = int(k), int(limit)
+        if not 0 <= k <= _lib.SDK_HIT_MAX_CLUES:
+            raise ValueError(f"k must be 0..{_lib.SDK_HIT_MAX_CLUES}")
+        if limit < 0 or int(max_waves) < 0:
+            raise ValueError("limit and max_waves must be >= 0")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        ctx = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        with torch.cuda.device(self.device), ctx():
+            offsets = self._dev(torch.as_tensor(offsets)).to(torch.int64).contiguous()
+            if offsets.dim() != 1 or offsets.shape[0] < 1:
+                raise ValueError("offsets must hold one entry per family and one more")
+            n = offsets.shape[0] - 1
+            s = self._dev(torch.as_tensor(sets))
+            if s.dim() != 2 or s.shape[1] not in (81, 3, 4):
+                raise ValueError("sets must be (S, 81) cells or packed (S, 3) words")
+            s = self._cell_masks(s, s.shape[0], "sets", 0) if s.shape[0] else torch.zeros((0, 4), dtype=torch.int32,
+                                                                                          device=self.device)
+            if n and (int(offsets[0].item()) != 0 or int(offsets[-1].item()) != s.shape[0]):
+                raise ValueError("offsets must start at 0 and end at the number of sets")
+            A = self._cell_masks(allowed, n, "allowed", (1 << 81) - 1)
+            R = self._cell_masks(required, n, "required", 0)
+            count = torch.zeros(n, dtype=torch.int64, device=self.device)
+            status = torch.zeros(n, dtype=torch.int32, device=self.device)
+            info = torch.zeros(2, dtype=torch.int64, device=self.device)
+            cap = HIT_CAPACITY if capacity is None else int(capacity)
+            for attempt in range(2):
+                rows = torch.empty((cap, 4), dtype=torch.int32, device=self.device)
+                with self._lock:
+                    sc = self._scratch("_hit_scratch", int(self.lib.sdk_hitting_sets_scratch_bytes(n, int(max_waves))))
+                    rc = self.lib.sdk_hitting_sets_batch(s.data_ptr() if s.shape[0] else None, offsets.data_ptr(),
+                                                         A.data_ptr(), R.data_ptr(), n, k, limit,
+                                                         rows.data_ptr() if cap else None, cap, count.data_ptr(),
+                                                         status.data_ptr(), info.data_ptr(), sc.data_ptr(), sc.numel(),
+                                                         int(max_waves), self._ws_stream(stream))
+                self._rc_only(rc, "sdk_hitting_sets_batch")
+                total, listed = (int(v) for v in info.tolist())
+                if listed == total or cap == 0:
+                    break
+                if capacity is not None:
+                    raise SudokuHipError(f"hitting_sets: the list overflowed, {total} rows asked for a slot and the "
+                                         f"capacity is {cap} (call again with capacity={total})")
+                cap = total
+            if not return_status and n and bool((status == SDK_INVALID).any().item()):
+                raise SudokuHipError(f"hitting_sets: {int((status == SDK_INVALID).sum().item())} of {n} families have "
+                                     f"masks that are no cell sets (return_status=True gives the statuses)")
+            # one sort for the order: rows of (family, the three words bit-reversed and negated, so that the set holding
+            # the lowest cell two sets differ in comes first) compared lexicographically
+            w = rows[:listed].to(torch.int64) & 0xFFFFFFFF
+            keys = torch.stack([w[:, 3]] + [0xFFFFFFFF - self._rev32(w[:, j]) for j in range(3)], dim=1)
+            if listed:
+                keys = torch.unique(keys, dim=0)
+            owner = keys[:, 0]
+            words = torch.stack([self._rev32(0xFFFFFFFF - keys[:, 1 + j]) for j in range(3)], dim=1)
+            out_offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            if n:
+                out_offsets[1:] = torch.cumsum(torch.bincount(owner, minlength=n), dim=0)
+            if packed:
+                out = (words - ((words >> 31) << 32)).to(torch.int32).contiguous()
+            else:
+                cells = torch.arange(81, device=self.device)
+                out = ((words[:, cells >> 5] >> (cells & 31)) & 1).to(torch.uint8)
+        return (out, out_offsets) + ((status,) if return_status else ()) + ((count,) if return_count else ())
+
+    def sub_puzzles(self, grids, k: int, allowed=None, required=None, max_size: int = 12, sets=None, chunk: int = 1 << 18,
+                    stream=None, max_waves: int = 0):
+        """Every proper puzzle of exactly k clues whose solution is grid i,
+        with required[i] <= its clue cells <= allowed[i] (masks as in
+        hitting_sets), as (puzzles (R, 81) uint8, offsets (n + 1,) int64),
+        ordered by grid and then by ascending clue cells.  A proper puzzle has
+        a clue in every unavoidable set of its grid, so the candidates are the
+        k-cell hitting sets of the grid's minimal unavoidable sets of at most
+        max_size cells (BatchSolver.unavoidable, or `sets` = (sets, offsets)
+        already computed for these grids); each candidate becomes a board by
+        tensor operations and is kept where count_solutions(limit=2) is 1.
+        The answer is exact for every max_size -- the sets only prune.  The
+        grids are counted first and listed in groups of at most `chunk`
+        candidates (a grid with more has a group to itself), and boards are
+        built and verified `chunk` at a time, so memory stays bounded by the
+        largest grid's packed candidates; a grid with more than
+        SUB_PUZZLES_MAX_ROWS of them raises SudokuHipError."""
+        g = self._dev(as_boards(grids, max_value=255))
+        n = g.shape[0]
+        ctx = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        with torch.cuda.device(self.device), ctx():
+            if sets is None:
+                sets = self.unavoidable(g, max_size=max_size, packed=True, stream=stream, max_waves=max_waves)
+            usets, uoff = self._dev(sets[0]), self._dev(sets[1]).to(torch.int64)
+            A = self._cell_masks(allowed, n, "allowed", (1 << 81) - 1)
+            R = self._cell_masks(required, n, "required", 0)
+            kw = dict(stream=stream, max_waves=max_waves)
+            count = self.hitting_sets(usets, uoff, k, allowed=A, required=R, capacity=0, return_count=True, **kw)[2].tolist()
+            if count and max(count) > SUB_PUZZLES_MAX_ROWS:
+                raise SudokuHipError(f"sub_puzzles: grid {count.index(max(count))} has {max(count)} candidates of {k} cells, more "
+                                     f"than {SUB_PUZZLES_MAX_ROWS} (16 bytes each in one list): narrow allowed, widen required "
+                                     f"or raise max_size")
+            cells = torch.arange(81, device=self.device)
+            found, per = [], torch.zeros(n, dtype=torch.int64, device=self.device)
+            lo = 0
+            while lo < n:
+                hi, rows = lo + 1, count[lo]
+                while hi < n and rows + count[hi] <= chunk:
+                    rows += count[hi]
+                    hi += 1
+                if rows:
+                    part, poff = self.hitting_sets(usets[uoff[lo]:uoff[hi]], uoff[lo:hi + 1] - uoff[lo], k, allowed=A[lo:hi],
+                                                   required=R[lo:hi], packed=True, capacity=rows, **kw)
+                    owner = torch.repeat_interleave(torch.arange(lo, hi, device=self.device), poff[1:] - poff[:-1])
+                    for at in range(0, part.shape[0], chunk):
+                        w = part[at:at + chunk].to(torch.int64) & 0xFFFFFFFF
+                        own = owner[at:at + chunk]
+                        boards = g[own] * ((w[:, cells >> 5] >> (cells & 31)) & 1).to(torch.uint8)
+                        good = self.count_solutions(boards, limit=2, **kw) == 1
+                        found.append(boards[good])
+                        per.index_add_(0, own[good], torch.ones_like(own[good]))
+                lo = hi
+            puzzles = torch.cat(found) if found else torch.zeros((0, 81), dtype=torch.uint8, device=self.device)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            offsets[1:] = torch.cumsum(per, dim=0)
+        return puzzles, offsets
 
     # ---------------------------------------------------------- backdoors
     def backdoors(self, boards, level: int = 2, max_size: int = 3, solutions=None, return_count: bool = False,
