@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "../../sudoku_solver_distributed_amd/csrc/common.h"  // SDK_PLANE_LOCKTBL's default: the kernel's pass
 #include "../../sudoku_solver_distributed_amd/csrc/plane_solver.h"
 
 #ifndef WPE
@@ -29,7 +30,16 @@ __global__ __launch_bounds__(256, WPE) void pass_loop(const uint32_t *boards, ui
 #pragma unroll
     for (int b = 0; b < 3; ++b) und[b] = plane::andn(plane::ROWS, nd[b]);
     uint32_t acc = 0;
+#if SDK_PLANE_LOCKTBL
+    // rule D's box -> row form from the LDS table, one per 256-thread block as in the plane kernel
+    // (-DSDK_PLANE_LOCKTBL_GROUP=1 / 9 / 27: lookups in flight)
+    __shared__ uint32_t tbl[plane::LOCK_ENTRIES];
+    plane::lock_fill(tbl, threadIdx.x, 256);
+    __syncthreads();
+    for (int it = 0; it < ITER; ++it) acc += (uint32_t)plane::pass_ahead(B, und, nd, tbl) + und[0] + und[1] + und[2];
+#else
     for (int it = 0; it < ITER; ++it) acc += (uint32_t)plane::pass_ahead(B, und, nd) + und[0] + und[1] + und[2];
+#endif
     sink[g] = acc;
 }
 

@@ -67,6 +67,8 @@ VARIANTS = {
     "waves5": (("SDK_PLANE_WAVES_PER_EU=5",), _SCHED),
     "waves6": (("SDK_PLANE_WAVES_PER_EU=6",), _SCHED),
     "nopinacc": (("SDK_PLANE_PIN_ACC=0",), _SCHED),
+    # rule D's box -> row form computed per word, one-wave workgroups (the kernel before the LDS table)
+    "locktbl-off": (("SDK_PLANE_LOCKTBL=0",), _SCHED),
     "sched-default": ((), "default"),
     "sched-minreg": ((), "iterative-minreg"),
     "sched-maxocc": ((), "iterative-maxocc"),

@@ -120,12 +120,23 @@ hipError_t sdk_launch_plane_multi(const PlaneBatches &bs, unsigned long long *ws
                                   int64_t *defer_list, int order, int64_t threads, int pipelined, hipStream_t st);
 int sdk_plane_blocks_per_cu();
 #define PLANE_MAX_DEPTH 32
-// plane kernel workgroup: ONE wave.  Its waves share nothing (each has its
-// own LDS areas), and a one-wave workgroup frees its LDS the moment its wave
-// exits, so during a launch's drain the next launch in flight starts wave by
-// wave instead of block by block (+3 %; 256 = the former 4-wave block)
+// SDK_PLANE_LOCKTBL 1: the plane kernel's pass takes rule D's box -> row form
+// from a 512-entry table in LDS (plane_solver.h lock_fill / lock_offset)
+// instead of computing it per word; 0: the arithmetic (point_rows_apply)
+#ifndef SDK_PLANE_LOCKTBL
+#define SDK_PLANE_LOCKTBL 1
+#endif
+// plane kernel workgroup.  Without the table ONE wave: its waves share nothing
+// (each has its own LDS areas), and a one-wave workgroup frees its LDS the
+// moment its wave exits, so during a launch's drain the next launch in flight
+// starts wave by wave instead of block by block (+3 %; 256 = the former
+// 4-wave block).  With the table FOUR waves, which share the one table: a
+// wave's own areas take 9488 B and 16 of them 151.8 KB of the CU's 160 KB, so
+// a 2 KB table per wave would cost a wave per SIMD; 4 x (4 x 9488 + 2048) =
+// 160 000 B keeps four.  The waves still share nothing else, and meet at one
+// barrier only, after the fill.
 #ifndef SDK_PLANE_BLOCK
-#define SDK_PLANE_BLOCK 64
+#define SDK_PLANE_BLOCK (SDK_PLANE_LOCKTBL ? 256 : 64)
 #endif
 #define PLANE_THREADS SDK_PLANE_BLOCK
 #define PLANE_STACK_WORDS 32  // per level: 27 planes + branch entry, padded to one 128-byte line

@@ -19,9 +19,12 @@
 // wave's chunk records in LDS (each claimed chunk staged as one span and
 // converted lane-parallel to value bit-slices once; a refilled lane reads
 // its record and builds its planes).  Boards come from a static first
-// hand-out and then chunked claims on one queue head.  A workgroup is one
-// wave: the waves share nothing, and a finished wave frees its LDS at once
-// for the next launch in flight (BatchSolver.solve_inflight).
+// hand-out and then chunked claims on one queue head.  A workgroup is four
+// waves that share one thing, read-only: the 2 KB table of the pass's rule D
+// box -> row form (plane::lock_fill, SDK_PLANE_LOCKTBL; one barrier after the
+// fill, none in the lane loop).  Without the table (SDK_PLANE_LOCKTBL=0) a
+// workgroup is one wave, which frees its LDS at once for the next launch in
+// flight (BatchSolver.solve_inflight).
 //
 // Once the queue is empty, a wave down to SDK_PLANE_TAIL boards hands them to
 // the wave-wide solver (plane_wide.h): each board in turn is spread over the
@@ -762,8 +765,19 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
     __shared__ uint32_t lds_pad[PLANE_THREADS / 64][SDK_PLANE_LDS_PAD];  // A/B: occupancy by LDS
     asm volatile("" ::"v"((uint32_t)(uintptr_t)&lds_pad[0][0]));
 #endif
-    uint32_t *stage = stage_lds[threadIdx.x >> 6];
-    uint32_t *outbox = outbox_lds[threadIdx.x >> 6];
+#if SDK_PLANE_LOCKTBL
+    // rule D's box -> row table, one for the workgroup's waves: filled here,
+    // before anything else, so that EVERY wave reaches the barrier (one whose
+    // first boards lie past n too); the lane loop below has none
+    __shared__ uint32_t lock_lds[plane::LOCK_ENTRIES];
+    plane::lock_fill(lock_lds, threadIdx.x, PLANE_THREADS);
+    __syncthreads();
+#endif
+    // (the wave's index as a scalar: from threadIdx.x alone the LDS bases of a
+    // four-wave workgroup are per-lane values, and plane_kernel spills 48 VGPRs)
+    const uint32_t wv = PLANE_THREADS > 64 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
+    uint32_t *stage = stage_lds[wv];
+    uint32_t *outbox = outbox_lds[wv];
     uint32_t ob_count = 0;  // boards waiting in the outbox (wave-uniform)
     if ((threadIdx.x & 63) == 0) stage[PLANE_STAGE_DWORDS - 1] = 0u;  // the zero byte
     const int64_t nt = (int64_t)gridDim.x * PLANE_THREADS;
@@ -1096,7 +1110,11 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
         st_lanes += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
         st_piters++;
 #endif
+#if SDK_PLANE_LOCKTBL
+        const int r = plane::pass_ahead(B, und, nd, lock_lds);
+#else
         const int r = plane::pass_ahead(B, und, nd);
+#endif
         if (r == plane::STUCK && best && __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p) {
             state = PL_CANCELLED;  // ordered mode: a lower board is solved
             continue;

@@ -230,6 +230,62 @@ PS_FN uint32_t point_rows_apply(uint32_t y)
     return PS_BOP3(0xB0, y, rows, area, y & ~(rows & ~area));  // y & (~rows | area)
 }
 
+// ---- rule D, box -> row, as a table lookup (the plane kernel's pass only)
+// What point_rows() clears from a band word depends only on which of the
+// word's nine mini-rows (row k of box j: cells 10k + 3j .. 10k + 3j + 2) hold
+// a place: a 9-bit pattern.  So point_rows_apply(y) == y & tbl[lock_index(y)]
+// with a 512-entry table of 27-bit keep masks (lock_entry), which the plane
+// kernel keeps in LDS (lock_fill at its start): 9 VALU and one LDS read per
+// word where the arithmetic takes 16 (tests/test_lock_table.py holds the two
+// equal on every 27-bit word).  Every other caller keeps point_rows_apply.
+enum { LOCK_ENTRIES = 512 };
+// (the plane kernel's choice: SDK_PLANE_LOCKTBL, common.h.)
+// SDK_PLANE_LOCKTBL_GROUP: lookups in flight at once (1: read, wait, AND word
+// by word; 9; 27: every read issued, then the ANDs)
+#ifndef SDK_PLANE_LOCKTBL_GROUP
+#define SDK_PLANE_LOCKTBL_GROUP 9
+#endif
+// 2x as an add (full rate; LLVM turns x + x into the half-rate v_lshlrev_b32)
+PS_FN uint32_t twice(uint32_t x)
+{
+#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_add_u32 %0, %1, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return x + x;
+#endif
+}
+// 4 * lock_index(y), the entry's byte offset: mini-row (k, j)'s flag is made
+// at bit 10k + 3j + 2 and folded down to bit 2 + 3j + k -- adds, right shifts
+// and literal masks only
+PS_FN uint32_t lock_offset(uint32_t y)
+{
+    const uint32_t y2 = twice(y), y4 = twice(y2);
+    const uint32_t r3 = or3(y, y2, y4) & (0x4912449u << 2);  // mini-row (k, j) has a place: bit 10k + 3j + 2
+    return or3(r3, r3 >> 9, r3 >> 18) & 0x7FCu;
+}
+// the table index of band word y: bit 3j + k = row k of box j holds a place
+PS_FN uint32_t lock_index(uint32_t y) { return lock_offset(y) >> 2; }
+// entry i: the cells a word with mini-row pattern i keeps (guard bits clear)
+PS_FN uint32_t lock_entry(uint32_t i)
+{
+    uint32_t rep = 0;  // all three cells of every mini-row i marks occupied
+    for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k)
+            if ((i >> (3 * j + k)) & 1u) rep |= 7u << (10 * k + 3 * j);
+    return ROWS & ~point_rows(rep);
+}
+// thread `tid` of `nthreads` fills its share of the table
+PS_FN void lock_fill(uint32_t *tbl, uint32_t tid, uint32_t nthreads)
+{
+    for (uint32_t i = tid; i < (uint32_t)LOCK_ENTRIES; i += nthreads) tbl[i] = lock_entry(i);
+}
+PS_FN uint32_t lock_read(const uint32_t *tbl, uint32_t off)
+{
+    return *(const uint32_t *)((const unsigned char *)tbl + off);
+}
+
 PS_FN uint32_t spread_rows(uint32_t c) { return c | (c << 10) | (c << 20); }  // 9-bit column set -> 3 rows
 PS_FN uint32_t guard_rows(uint32_t g) { return g - (g >> 9); }               // guard flags -> whole rows
 PS_FN uint32_t row_nonzero(uint32_t y) { return (y + ROWS) & GUARDS; }        // guard set iff row != 0
@@ -272,8 +328,11 @@ PS_FN uint32_t rule_a(const Board &B, uint32_t (&single)[3])
 // with literal constants, three-input logic as v_bitop3_b32 on VGPRs, right
 // shifts only, 16-bit multiplies for 9-bit results, and one v_mul_u32_u24
 // per spread of a set over a band's three rows.  With rule A, 1797 VALU per
-// pass with SDK_PLANE_LC 3 (profiles/isa_plane_pass.json).
-PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
+// pass with SDK_PLANE_LC 3, 1602 with the table (profiles/isa_plane_pass.json).
+// TBL: rule D's box -> row form from the table `tbl` (lock_fill) instead of
+// point_rows_apply -- the same planes (pass_body(B, nd, hall, tbl) below).
+template <bool TBL>
+PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3], const uint32_t *tbl)
 {
     hall[0] = hall[1] = hall[2] = 0u;
 #if SDK_PLANE_GROUP > 1
@@ -432,7 +491,30 @@ PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
         }
     }
 #if SDK_PLANE_LC & 2
-    {
+    if constexpr (TBL) {
+        // rule D's box -> row form looked up: the offsets of a group of
+        // words, their reads all in flight, then the ANDs (the pins keep the
+        // three stages apart, so the reads' latency is paid once per group)
+        constexpr int G = SDK_PLANE_LOCKTBL_GROUP;
+        static_assert(G >= 1 && 27 % G == 0, "SDK_PLANE_LOCKTBL_GROUP divides 27");
+#pragma unroll
+        for (int g = 0; g < 27; g += G) {
+            uint32_t off[G], keep[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) off[i] = lock_offset(B.P[(g + i) / 3][(g + i) % 3]);
+#pragma unroll
+            for (int i = 0; i < G; ++i) PS_PIN(off[i]);
+#pragma unroll
+            for (int i = 0; i < G; ++i) keep[i] = lock_read(tbl, off[i]);
+#pragma unroll
+            for (int i = 0; i < G; ++i) PS_PIN(keep[i]);
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                B.P[(g + i) / 3][(g + i) % 3] &= keep[i];
+                PS_PIN(B.P[(g + i) / 3][(g + i) % 3]);
+            }
+        }
+    } else {
         // rule D's box -> row form, after the digit loop (its registers are
         // free again): every plane word once
 #pragma unroll
@@ -444,14 +526,24 @@ PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
             }
     }
 #endif
+    (void)tbl;
     return or3(rowall ^ GUARDS, colall ^ 0x1FFu, (boxall & BOXC) ^ BOXC);
+}
+PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
+{
+    return pass_body_t<false>(B, nd, hall, nullptr);
+}
+PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3], const uint32_t *tbl)
+{
+    return pass_body_t<true>(B, nd, hall, tbl);
 }
 
 // One propagation pass (rules A-D above), rule A first, on the state the
 // previous pass left.  Returns DEAD, SOLVED, STUCK (no single found: und[] =
 // the undetermined cells; rule D may still have removed places, which the
 // next pass sees) or OPEN (pass again).
-PS_FN int pass(Board &B, uint32_t und[3])
+template <bool TBL>
+PS_FN int pass_t(Board &B, uint32_t und[3], const uint32_t *tbl)
 {
     uint32_t single[3], nd[3], hall[3];
     uint32_t dead = rule_a(B, single);
@@ -464,7 +556,7 @@ PS_FN int pass(Board &B, uint32_t und[3])
     const bool all_single = and3(single[0], single[1], single[2]) == ROWS;
     const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
     pin_board(B);
-    dead |= pass_body(B, nd, hall);
+    dead |= pass_body_t<TBL>(B, nd, hall, tbl);
     if (dead) return DEAD;
     if (all_single) return SOLVED;
     const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
@@ -474,6 +566,9 @@ PS_FN int pass(Board &B, uint32_t und[3])
     // change tracking, 27 VALU)
     return (any_nd || newh) ? OPEN : STUCK;
 }
+PS_FN int pass(Board &B, uint32_t und[3]) { return pass_t<false>(B, und, nullptr); }
+// the same pass with rule D's box -> row form from the table (lock_fill)
+PS_FN int pass(Board &B, uint32_t und[3], const uint32_t *tbl) { return pass_t<true>(B, und, tbl); }
 
 // The look-ahead pass: the same body, then rule A on the planes it leaves, so
 // the pass settles its own verdict instead of leaving it to the next one (a
@@ -485,12 +580,13 @@ PS_FN int pass(Board &B, uint32_t und[3])
 // digit, or a cell is empty now; SOLVED: no cell was undetermined on entry
 // (this was the verifying pass); STUCK: no cell became determined and no
 // hidden single was placed; OPEN otherwise.
-PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3])
+template <bool TBL>
+PS_FN int pass_ahead_t(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const uint32_t *tbl)
 {
     uint32_t single[3], hall[3];
     const bool all_single = or3(und[0], und[1], und[2]) == 0;
     pin_board(B);
-    uint32_t dead = pass_body(B, nd, hall);
+    uint32_t dead = pass_body_t<TBL>(B, nd, hall, tbl);
     const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
     dead |= rule_a(B, single);
 #pragma unroll
@@ -502,6 +598,15 @@ PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3])
     if (all_single) return SOLVED;
     const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
     return (any_nd || newh) ? OPEN : STUCK;
+}
+PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3])
+{
+    return pass_ahead_t<false>(B, und, nd, nullptr);
+}
+// the same pass with rule D's box -> row form from the table (lock_fill)
+PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const uint32_t *tbl)
+{
+    return pass_ahead_t<true>(B, und, nd, tbl);
 }
 
 // The walk's branch cell among the undetermined cells: node.py:63-65 takes
