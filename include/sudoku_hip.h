@@ -391,6 +391,78 @@ int sdk_rate_batch(const uint8_t *d_boards, int32_t *d_rating, int32_t *d_open /
                    uint16_t *d_marks /* n*81, NULL ok */, int64_t n, int max_level, void *d_scratch,
                    size_t scratch_bytes, void *stream);
 
+/* Named techniques: which of the human rules -- singles, locked candidates,
+ * subsets, fish -- n states fall to (library extension, no reference
+ * counterpart).  The state, dead and solved, and the rules N,
+ * H and L are sdk_rate_batch's.  The Hall step of size k on a 9x9 0/1 matrix
+ * with row sets M[0..8]: for every k-subset I of rows, with u the union of
+ * its rows, |u| < k makes the state dead (pigeonhole) and |u| == k takes u
+ * out of every row outside I; rows of any size take part.
+ *   S_k  subsets, k = 2, 3, 4: in each of the 27 units the step on cells x
+ *        candidate digits (naked pairs, triples, quads) and on digits x the
+ *        cells where the digit has a place (hidden ones);
+ *   F_k  fish, k = 2, 3, 4: for each digit the step on rows x the columns
+ *        where it has a place and on columns x rows (X-wing, swordfish,
+ *        jellyfish, both orientations).
+ * Every rule only removes candidates and is monotone with dead as the bottom
+ * state, so the fixpoint of a rule set depends on no order.
+ * A rule set is a bit mask of SDK_LOGIC_N .. SDK_LOGIC_F4; `ladder` (HOST
+ * memory, read before the call returns) holds `steps` of them, 1 <= steps <=
+ * SDK_LOGIC_MAX_STEPS, each with SDK_LOGIC_N and a proper superset of the one
+ * before; closure_j is the fixpoint of step j's rules, or dead.  The default
+ * ladder is {N, N|H, N|H|L, +S2, +S3|S4, +F2, +F3|F4}: singles, hidden
+ * singles, locked candidates, pairs, triples / quads, X-wing, swordfish /
+ * jellyfish, and step 8: beyond.
+ * State i starts as board i's start state (d_boards NULL: every board empty)
+ * ANDed with the pencil marks d_start[81 i + c] (bit d-1 for digit d;
+ * d_start NULL: every mask 0x1FF).  Both NULL is a bad argument.
+ *   d_step[i]         = the lowest j (1-based) with closure_j solved; 0 when
+ *                       some computed closure is dead; steps + 1 otherwise;
+ *   d_open[8 i + j-1] = the cells of closure_j without exactly one candidate;
+ *                       0 from the solving step on, -1 from the dead step
+ *                       on, SDK_LOGIC_NOT_RUN past `steps`;
+ *   d_left[8 i + j-1] = the candidates closure_j leaves over all 81 cells; 81
+ *                       from the solving step on, -1 from the dead step on,
+ *                       SDK_LOGIC_NOT_RUN past `steps` (d_open does not see
+ *                       a removal that empties no cell);
+ *   d_marks[81 i + c] = the candidates of cell c in the deepest closure
+ *                       computed; all zero when that closure is dead.
+ * A byte > 9 or a mark with a bit above 0x1FF gives SDK_INVALID in d_step[i]
+ * and all eight d_open and d_left entries, and zero marks.  d_open, d_left
+ * and d_marks may be NULL; d_start and d_marks need 2-byte alignment,
+ * d_boards none.  Inputs are never modified and no byte outside these
+ * extents is written.
+ * d_scratch: at least sdk_logic_scratch_bytes(n, steps) bytes of device
+ * memory, 8-byte aligned, contents irrelevant: the call re-arms its counters
+ * itself on `stream` (256 bytes, and eight bytes per board: the list of the
+ * boards the leading N / N|H / N|H|L steps leave open).  SINGLE-STREAM like a
+ * workspace; the solve workspace is not involved.
+ * Asynchronous on `stream`.  Returns 0 / -1 (HIP error) / -2 (bad arguments:
+ * steps out of range, a mask outside 0x1FF or without N, a step that is not a
+ * proper superset of the one before, both inputs NULL, n negative or above
+ * 2^31 - 1, a NULL pointer that is required, a misaligned pointer, scratch
+ * too small), by return code only; arguments are checked before any launch
+ * and n == 0 returns 0 once n and the ladder are checked.
+ * sdk_logic_scratch_bytes returns 0 for bad arguments (n above 2^31 - 1 among
+ * them). */
+#define SDK_LOGIC_MAX_STEPS 8
+#define SDK_LOGIC_NOT_RUN -2
+#define SDK_LOGIC_N 1
+#define SDK_LOGIC_H 2
+#define SDK_LOGIC_L 4
+#define SDK_LOGIC_S2 8
+#define SDK_LOGIC_S3 16
+#define SDK_LOGIC_S4 32
+#define SDK_LOGIC_F2 64
+#define SDK_LOGIC_F3 128
+#define SDK_LOGIC_F4 256
+size_t sdk_logic_scratch_bytes(int64_t n, int steps);
+int sdk_logic_batch(const uint8_t *d_boards /* NULL ok */, const uint16_t *d_start /* NULL ok */,
+                    const uint32_t *ladder /* HOST memory, `steps` words */, int steps,
+                    int32_t *d_step, int32_t *d_open /* n*8, NULL ok */, int32_t *d_left /* n*8, NULL ok */,
+                    uint16_t *d_marks /* n*81, NULL ok */, int64_t n,
+                    void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* The exact candidates of n boards (library extension, no reference
  * counterpart).  A completion of a board is a valid Sudoku grid -- every row,
  * column and box holds 1..9 once -- that keeps the givens.

@@ -50,6 +50,8 @@ EXPORTS = (
     "sdk_canonical_batch",
     "sdk_rate_scratch_bytes",
     "sdk_rate_batch",
+    "sdk_logic_scratch_bytes",
+    "sdk_logic_batch",
     "sdk_candidates_scratch_bytes",
     "sdk_candidates_batch",
     "sdk_minimize_scratch_bytes",
@@ -77,6 +79,11 @@ SDK_CANON_SYMMETRIES = 3359232  # sdk_canonical_batch: 2 * 1296 * 1296
 SDK_CANON_MAX_SLICES = 2592  # ... and the most parts a board's search is cut into
 SDK_RATE_MAX_LEVEL = 4  # sdk_rate_batch: the deepest rule level (trial eliminations)
 SDK_RATE_NOT_RUN = -2  # ... and the open count of a level above max_level
+SDK_LOGIC_MAX_STEPS = 8  # sdk_logic_batch: the most steps of a ladder
+SDK_LOGIC_NOT_RUN = -2  # ... and the open / left count of a step past the ladder's end
+# ... its rules: naked singles, hidden singles, locked candidates, subsets of 2..4, fish of 2..4
+(SDK_LOGIC_N, SDK_LOGIC_H, SDK_LOGIC_L, SDK_LOGIC_S2, SDK_LOGIC_S3, SDK_LOGIC_S4, SDK_LOGIC_F2, SDK_LOGIC_F3,
+ SDK_LOGIC_F4) = (1 << k for k in range(9))
 SDK_MIN_GREEDY = 0  # sdk_minimize_batch: erase givens turn by turn while one completion is left
 SDK_MIN_PROBE = 1   # ... or test every given alone against the input board
 SDK_EXACT_DONE = 1     # sdk_count_exact_batch: the count is exact
@@ -165,6 +172,10 @@ def load() -> ctypes.CDLL:
     L.sdk_rate_scratch_bytes.argtypes = [i64, i32]
     L.sdk_rate_batch.restype = i32
     L.sdk_rate_batch.argtypes = [vp, vp, vp, vp, i64, i32, vp, sz, vp]
+    L.sdk_logic_scratch_bytes.restype = sz
+    L.sdk_logic_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_logic_batch.restype = i32
+    L.sdk_logic_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, sz, vp]
     L.sdk_candidates_scratch_bytes.restype = sz
     L.sdk_candidates_scratch_bytes.argtypes = [i64, i32]
     L.sdk_candidates_batch.restype = i32

@@ -25,7 +25,8 @@ ROOT = os.path.dirname(_HERE)
 # backdoor_kernels.hip, the backdoor search on the rating's closures, a unit of
 # its own like rate_kernels.hip, LLVM's defaults, §23; ua_kernels.hip, the
 # unavoidable sets of a grid, likewise, §24; hit_kernels.hip, the hitting
-# sets of a family of cell sets, likewise, §25)
+# sets of a family of cell sets, likewise, §25; logic_kernels.hip, the named
+# techniques on the rating's closures, likewise, §26)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -53,7 +54,8 @@ def sources(sched: str = _SCHED):
             ("enum_kernels.hip", ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]),
             ("backdoor_kernels.hip", []),
             ("ua_kernels.hip", []),
-            ("hit_kernels.hip", []))
+            ("hit_kernels.hip", []),
+            ("logic_kernels.hip", []))
 
 
 SRCS = sources()

@@ -251,6 +251,24 @@ def rated_batch(n: int, seed: Optional[int] = None, ratings=None, device=None, r
     return (puzzles, rating, full) if return_solutions else (puzzles, rating)
 
 
+# what BatchSolver.logic's step says at the default ladder: GRADE_NAMES[step]
+GRADE_NAMES = ("dead", "singles", "hidden singles", "locked candidates", "pairs", "triples / quads", "X-wing",
+               "swordfish / jellyfish", "beyond")
+
+
+def grade(boards, device=None) -> torch.Tensor:
+    """The first step of the default ladder that solves every board
+    (BatchSolver.logic): 1 singles .. 7 swordfish / jellyfish, 8 beyond them,
+    0 no completion, as an int32 (n,) device tensor; grade_names() gives the
+    names.  Library extension, no reference counterpart."""
+    return get_solver(device).logic(boards)
+
+
+def grade_names(steps) -> List[str]:
+    """GRADE_NAMES for grade()'s steps ("invalid" for SDK_INVALID)."""
+    return [GRADE_NAMES[s] if 0 <= s < len(GRADE_NAMES) else "invalid" for s in torch.as_tensor(steps).cpu().tolist()]
+
+
 def make_unique(boards, device=None):
     """Boards with several completions turned into proper puzzles by adding
     givens: (puzzles (n, 81) uint8, added (n,) int32), device tensors.  Library

@@ -35,6 +35,10 @@ UA_CAPACITY = {4: 32, 5: 32, 6: 162, 7: 162, 8: 170, 9: 330, 10: 578, 11: 1818, 
 HIT_CAPACITY = 1 << 16
 # the most candidates of one grid sub_puzzles lists (4 GiB of packed rows); more raises instead of an allocation failure
 SUB_PUZZLES_MAX_ROWS = 1 << 28
+# logic's rules (SDK_LOGIC_*: naked singles, hidden singles, locked candidates, subsets of 2..4, fish of 2..4) and
+# the default ladder: singles, hidden singles, locked candidates, pairs, triples / quads, X-wing, swordfish / jellyfish
+N, H, L, S2, S3, S4, F2, F3, F4 = (1 << k for k in range(9))
+DEFAULT_LADDER = (N, N | H, N | H | L, N | H | L | S2, N | H | L | S2 | S3 | S4, N | H | L | S2 | S3 | S4 | F2, 0x1FF)
 
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
@@ -147,6 +151,7 @@ class BatchSolver:
         self._count_scratch = None  # count_solutions' scratch, grown on demand (under self._lock)
         self._canon_scratch = None  # canonical's scratch, likewise
         self._rate_scratch = None  # rate's scratch, likewise
+        self._logic_scratch = None  # logic's scratch, likewise
         self._cand_scratch = None  # candidates' scratch, likewise
         self._min_scratch = None  # minimize's scratch, likewise
         self._sample_scratch = None  # sample's scratch, likewise
@@ -455,6 +460,64 @@ class BatchSolver:
         self._rc_only(rc, "sdk_rate_batch")
         out = (rating,) + ((opens,) if return_open else ()) + ((marks,) if return_marks else ())
         return out if len(out) > 1 else rating
+
+    # -------------------------------------------------------------- logic
+    def logic(self, boards=None, ladder=None, start=None, return_open: bool = False, return_left: bool = False,
+              return_marks: bool = False, stream=None):
+        """Which named technique every state falls to, as an int32 (n,)
+        tensor (sdk_logic_batch; library extension, no reference counterpart;
+        the definition is in include/sudoku_hip.h and DESIGN.md §26).  ladder:
+        1..8 rule sets (masks of N, H, L, S2, S3, S4, F2, F3, F4 below), each
+        with N and a proper superset of the one before; None is
+        DEFAULT_LADDER -- singles, hidden singles, locked candidates, pairs,
+        triples / quads, X-wing, swordfish / jellyfish.  The answer is the
+        first step (1-based) whose rules solve the state, 0 when some step
+        proves that it has no completion, len(ladder) + 1 when the ladder
+        does not decide it; it depends on no order of the rules and is the
+        same for every symmetry image.  start: pencil marks, (n, 81) int16
+        masks (bit d-1 for digit d) ANDed into the boards' start states;
+        boards None: empty boards under `start`.  return_open / return_left:
+        also int32 (n, 8) tensors, per step the cells without exactly one
+        candidate and the candidates left in all (0 and 81 from the solving
+        step on, -1 from the dead step on, SDK_LOGIC_NOT_RUN (-2) past the
+        ladder's end); return_marks: also an int16 (n, 81) tensor, the
+        candidates the deepest closure computed leaves (zero when dead).  A
+        byte > 9 or a mark above 0x1FF gives SDK_INVALID (-1) in the step
+        and the counts.  Asynchronous on the stream; one cached scratch
+        tensor serves every call, ordered like the workspace's."""
+        lad = [int(m) for m in (DEFAULT_LADDER if ladder is None else ladder)]
+        if not 1 <= len(lad) <= _lib.SDK_LOGIC_MAX_STEPS:
+            raise ValueError(f"a ladder has 1..{_lib.SDK_LOGIC_MAX_STEPS} steps")
+        for prev, m in zip([0] + lad, lad):
+            if m & ~0x1FF or not m & N or m == prev or m & prev != prev:
+                raise ValueError("every step of a ladder is a mask inside 0x1FF with N and a proper superset of the step before")
+        if boards is None and start is None:
+            raise ValueError("logic needs boards, start or both")
+        p = self._dev(as_boards(boards, max_value=255)) if boards is not None else None
+        s = None
+        if start is not None:
+            s = torch.as_tensor(start)
+            if s.dtype not in (torch.int16, torch.uint16):
+                s = s.to(torch.int16)
+            s = self._dev(s.reshape(-1, 81))
+        n = p.shape[0] if p is not None else s.shape[0]
+        if p is not None and s is not None and s.shape[0] != n:
+            raise ValueError("boards and start differ in length")
+        step = torch.empty(n, dtype=torch.int32, device=self.device)
+        opens = torch.empty((n, 8), dtype=torch.int32, device=self.device) if return_open else None
+        left = torch.empty((n, 8), dtype=torch.int32, device=self.device) if return_left else None
+        marks = torch.empty((n, 81), dtype=torch.int16, device=self.device) if return_marks else None
+        host_ladder = (ctypes.c_uint32 * len(lad))(*lad)
+        with self._lock, torch.cuda.device(self.device):
+            sc = self._scratch("_logic_scratch", int(self.lib.sdk_logic_scratch_bytes(n, len(lad))))
+            rc = self.lib.sdk_logic_batch(p.data_ptr() if p is not None else None, s.data_ptr() if s is not None else None,
+                                          ctypes.addressof(host_ladder), len(lad), step.data_ptr(),
+                                          opens.data_ptr() if return_open else None, left.data_ptr() if return_left else None,
+                                          marks.data_ptr() if return_marks else None, n, sc.data_ptr(), sc.numel(),
+                                          self._ws_stream(stream))
+        self._rc_only(rc, "sdk_logic_batch")
+        out = (step,) + ((opens,) if return_open else ()) + ((left,) if return_left else ()) + ((marks,) if return_marks else ())
+        return out if len(out) > 1 else step
 
     # ---------------------------------------------------- unavoidable sets
     @staticmethod
