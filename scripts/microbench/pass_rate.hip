@@ -35,8 +35,18 @@ __global__ __launch_bounds__(256, WPE) void pass_loop(const uint32_t *boards, ui
     // (-DSDK_PLANE_LOCKTBL_GROUP=1 / 9 / 27: lookups in flight)
     __shared__ uint32_t tbl[plane::LOCK_ENTRIES];
     plane::lock_fill(tbl, threadIdx.x, 256);
+#if SDK_PLANE_COLTBL
+    // and rule C's box terms from the column table beside it (-DSDK_PLANE_COLTBL_GROUP=1 / 3 / 0)
+    __shared__ uint16_t ctbl[plane::COL_ENTRIES];
+    plane::col_fill(ctbl, threadIdx.x, 256);
+    __syncthreads();
+    const plane::PassTables T = {tbl, ctbl};
+    for (int it = 0; it < ITER; ++it)
+        acc += (uint32_t)plane::pass_ahead_tables<SDK_PLANE_COLTBL>(B, und, nd, T) + und[0] + und[1] + und[2];
+#else
     __syncthreads();
     for (int it = 0; it < ITER; ++it) acc += (uint32_t)plane::pass_ahead(B, und, nd, tbl) + und[0] + und[1] + und[2];
+#endif
 #else
     for (int it = 0; it < ITER; ++it) acc += (uint32_t)plane::pass_ahead(B, und, nd) + und[0] + und[1] + und[2];
 #endif

@@ -71,6 +71,8 @@ VARIANTS = {
     "nopinacc": (("SDK_PLANE_PIN_ACC=0",), _SCHED),
     # rule D's box -> row form computed per word, one-wave workgroups (the kernel before the LDS table)
     "locktbl-off": (("SDK_PLANE_LOCKTBL=0",), _SCHED),
+    # rule C's box terms computed per word (the kernel before the column table)
+    "coltbl-off": (("SDK_PLANE_COLTBL=0",), _SCHED),
     "sched-default": ((), "default"),
     "sched-minreg": ((), "iterative-minreg"),
     "sched-maxocc": ((), "iterative-maxocc"),

@@ -126,6 +126,23 @@ int sdk_plane_blocks_per_cu();
 #ifndef SDK_PLANE_LOCKTBL
 #define SDK_PLANE_LOCKTBL 1
 #endif
+// SDK_PLANE_COLTBL 1: the pass takes rule C's box terms too (the one-column
+// boxes' columns and the "box has a place" bits, functions of a band's nine
+// column-occupancy bits) from a 512-entry table of half-words in LDS beside
+// the lock table (plane_solver.h col_fill / col_offset); 0: the arithmetic.
+// Needs the lock table's four-wave workgroup.  The workgroup's LDS stays at
+// 40 960 B, four to a CU: the table's 1 KB is the 16 B per wave of the staging
+// area's former spare dword (plane_kernel.h PLANE_STAGE_DWORDS).
+#ifndef SDK_PLANE_COLTBL
+#define SDK_PLANE_COLTBL 1
+#endif
+#if SDK_PLANE_COLTBL && !SDK_PLANE_LOCKTBL
+#undef SDK_PLANE_COLTBL
+#define SDK_PLANE_COLTBL 0
+#endif
+#if SDK_PLANE_COLTBL > 1
+#error "SDK_PLANE_COLTBL: 0 or 1"
+#endif
 // plane kernel workgroup.  Without the table ONE wave: its waves share nothing
 // (each has its own LDS areas), and a one-wave workgroup frees its LDS the
 // moment its wave exits, so during a launch's drain the next launch in flight

@@ -20,9 +20,10 @@
 // converted lane-parallel to value bit-slices once; a refilled lane reads
 // its record and builds its planes).  Boards come from a static first
 // hand-out and then chunked claims on one queue head.  A workgroup is four
-// waves that share one thing, read-only: the 2 KB table of the pass's rule D
-// box -> row form (plane::lock_fill, SDK_PLANE_LOCKTBL; one barrier after the
-// fill, none in the lane loop).  Without the table (SDK_PLANE_LOCKTBL=0) a
+// waves that share one thing, read-only: the pass's tables -- 2 KB for rule
+// D's box -> row form (plane::lock_fill, SDK_PLANE_LOCKTBL) and 1 KB for rule
+// C's box terms (plane::col_fill, SDK_PLANE_COLTBL); one barrier after the
+// fill, none in the lane loop.  Without the tables (SDK_PLANE_LOCKTBL=0) a
 // workgroup is one wave, which frees its LDS at once for the next launch in
 // flight (BatchSolver.solve_inflight).
 //
@@ -236,10 +237,20 @@ struct PlaneIOn {
 // (a five-waves-per-SIMD budget, <= 8 KB of LDS per wave with 48-board
 // claims, a 56-board outbox and two start-up spans, measured -4 % / -9 % at
 // N = 1 / 8: the 96-VGPR limit spills 30 registers in the lane loop)
+// (With the column table, SDK_PLANE_COLTBL, the area is the 21 DMA rows alone:
+// nothing reads that zero byte any more, and its 16 B per wave are the table's
+// 1 KB per workgroup, common.h.)
+#if SDK_PLANE_COLTBL
 enum {
-    PLANE_STAGE_DWORDS = 1348, PLANE_STAGE_ZERO = 4 * (PLANE_STAGE_DWORDS - 1),
+    PLANE_STAGE_DWORDS = 1344, PLANE_STAGE_SPARE = 0,
     PLANE_START_SPAN = 64  // boards per staged span at start-up
 };
+#else
+enum {
+    PLANE_STAGE_DWORDS = 1348, PLANE_STAGE_ZERO = 4 * (PLANE_STAGE_DWORDS - 1), PLANE_STAGE_SPARE = 1,
+    PLANE_START_SPAN = 64  // boards per staged span at start-up
+};
+#endif
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 // s_waitcnt immediates (gfx9: vmcnt bits 3:0 + 15:14, expcnt 6:4, lgkmcnt 11:8)
@@ -306,8 +317,8 @@ __device__ __forceinline__ void plane_stage_words(const uint32_t *stage, uint32_
 // reads its own record at once, no per-board serial work.
 enum { PLANE_REC = 13, PLANE_CHUNK_MAX = 64 };
 static_assert(PLANE_CHUNK_MAX * PLANE_REC + 1 < PLANE_STAGE_DWORDS, "chunk records");
-static_assert((3 + 81 * PLANE_CHUNK_MAX + 3 + 255) / 256 * 64 < PLANE_STAGE_DWORDS, "a claimed chunk's span");
-static_assert((3 + 81 * PLANE_START_SPAN + 3 + 255) / 256 * 64 < PLANE_STAGE_DWORDS, "a start-up span");
+static_assert((3 + 81 * PLANE_CHUNK_MAX + 3 + 255) / 256 * 64 + PLANE_STAGE_SPARE <= PLANE_STAGE_DWORDS, "a claimed chunk's span");
+static_assert((3 + 81 * PLANE_START_SPAN + 3 + 255) / 256 * 64 + PLANE_STAGE_SPARE <= PLANE_STAGE_DWORDS, "a start-up span");
 
 __device__ __forceinline__ void plane_convert_chunk(uint32_t *stage, uint32_t sh, int count, int lane)
 {
@@ -427,7 +438,7 @@ __device__ __forceinline__ void plane_flush_outbox(const uint32_t *outbox, uint3
 // lo / hi, depth, stack line offset, guesses so far
 enum { PLANE_TAIL_REC = 33, PLANE_TAIL_MAX = 40 };  // word 32: the board's search mode (mst)
 // the last record, read up to word 48 (pad lanes), stays below the zero byte
-static_assert((PLANE_TAIL_MAX - 1) * PLANE_TAIL_REC + 48 < PLANE_STAGE_DWORDS - 1, "tail records");
+static_assert((PLANE_TAIL_MAX - 1) * PLANE_TAIL_REC + 48 < PLANE_STAGE_DWORDS - PLANE_STAGE_SPARE, "tail records");
 
 // The board's stack in the wide layout: lane 16b+d owns word 3d+b of each
 // level's line; the branch entry (word 27) goes through lane 48 (a pad lane)
@@ -771,6 +782,13 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
     // first boards lie past n too); the lane loop below has none
     __shared__ uint32_t lock_lds[plane::LOCK_ENTRIES];
     plane::lock_fill(lock_lds, threadIdx.x, PLANE_THREADS);
+#if SDK_PLANE_COLTBL
+    // rule C's box terms, beside it: the same fill, the same one barrier
+    __shared__ uint16_t col_lds[plane::COL_ENTRIES];
+    plane::col_fill(col_lds, threadIdx.x, PLANE_THREADS);
+    static_assert(sizeof stage_lds + sizeof outbox_lds + sizeof lock_lds + sizeof col_lds <= 40960 || SDK_PLANE_LDS_PAD,
+                  "four workgroups' LDS to a CU");
+#endif
     __syncthreads();
 #endif
     // (the wave's index as a scalar: from threadIdx.x alone the LDS bases of a
@@ -779,7 +797,9 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
     uint32_t *stage = stage_lds[wv];
     uint32_t *outbox = outbox_lds[wv];
     uint32_t ob_count = 0;  // boards waiting in the outbox (wave-uniform)
+#if !SDK_PLANE_COLTBL
     if ((threadIdx.x & 63) == 0) stage[PLANE_STAGE_DWORDS - 1] = 0u;  // the zero byte
+#endif
     const int64_t nt = (int64_t)gridDim.x * PLANE_THREADS;
     const int64_t g = (int64_t)blockIdx.x * PLANE_THREADS + threadIdx.x;
     PlaneStack stk = {
@@ -1110,7 +1130,9 @@ __device__ __forceinline__ void plane_body(const IO &io, unsigned long long *__r
         st_lanes += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
         st_piters++;
 #endif
-#if SDK_PLANE_LOCKTBL
+#if SDK_PLANE_COLTBL
+        const int r = plane::pass_ahead_tables<SDK_PLANE_COLTBL>(B, und, nd, plane::PassTables{lock_lds, col_lds});
+#elif SDK_PLANE_LOCKTBL
         const int r = plane::pass_ahead(B, und, nd, lock_lds);
 #else
         const int r = plane::pass_ahead(B, und, nd);

@@ -245,6 +245,13 @@ enum { LOCK_ENTRIES = 512 };
 #ifndef SDK_PLANE_LOCKTBL_GROUP
 #define SDK_PLANE_LOCKTBL_GROUP 9
 #endif
+// SDK_PLANE_COLTBL_GROUP: the column table's lookups (col_fill, below) in
+// flight at once (1: read and wait word by word; 2: a digit's three issued
+// together; 3: and used only after the row tests and column folds are made;
+// 0: no pins, the scheduler's own order)
+#ifndef SDK_PLANE_COLTBL_GROUP
+#define SDK_PLANE_COLTBL_GROUP 3
+#endif
 // 2x as an add (full rate; LLVM turns x + x into the half-rate v_lshlrev_b32)
 PS_FN uint32_t twice(uint32_t x)
 {
@@ -285,6 +292,54 @@ PS_FN uint32_t lock_read(const uint32_t *tbl, uint32_t off)
 {
     return *(const uint32_t *)((const unsigned char *)tbl + off);
 }
+
+// ---- rule C's box terms as a table lookup (the plane kernel's pass only)
+// Everything pass_body() derives from a band's column occupancy o & 0x1FF (bit
+// c: column c holds a place in the band) is a function of those nine bits:
+// vp, the columns of the boxes whose places lie in one column, and the three
+// "box has a place" bits that go into boxall.  col_entry(i) holds both in 16
+// bits -- vp in bits 0-8, the box bits moved up to bits 9 / 12 / 15 -- and the
+// plane kernel keeps the 512 entries (1 KB) in LDS beside the lock table
+// (col_fill): per word 2 VALU for the byte offset and one ds_read_u16, per
+// digit 3 more (boxall, vp's mask), where the arithmetic takes 8 per word.
+// The reads sit in the digit chain, so a digit's three are issued together
+// and the row tests and column folds, which do not need them, come before
+// their first use.  Every other caller keeps the arithmetic.
+enum { COL_ENTRIES = 512, COL_BOX_SHIFT = 9 };
+enum : uint32_t { COL_BOXES = (uint32_t)BOXC << COL_BOX_SHIFT };  // an entry's "box has a place" bits
+PS_FN uint32_t col_entry(uint32_t i)
+{
+    const uint32_t o = i & 0x1FFu, o1 = o >> 1, o2 = o >> 2;
+    const uint32_t ob = or3(o, o1, o2) & BOXC;                          // box bits 0/3/6: >= 1 place
+    const uint32_t vb = box_one(xor3(o, o1, o2), maj3(o, o1, o2));      // boxes with exactly one column
+    return (o & box_cols(vb)) | (ob << COL_BOX_SHIFT);
+}
+// thread `tid` of `nthreads` fills its share of the table
+PS_FN void col_fill(uint16_t *tbl, uint32_t tid, uint32_t nthreads)
+{
+    for (uint32_t i = tid; i < (uint32_t)COL_ENTRIES; i += nthreads) tbl[i] = (uint16_t)col_entry(i);
+}
+// 2 * (o & 0x1FF), the entry's byte offset (junk above bit 8 of o ignored)
+PS_FN uint32_t col_offset(uint32_t o) { return twice(o & 0x1FFu); }
+PS_FN uint32_t col_read(const uint16_t *tbl, uint32_t off)
+{
+    return *(const uint16_t *)((const unsigned char *)tbl + off);
+}
+// x & 0x1FF & ~m: one v_bitop3 with the mask in a VGPR
+PS_FN uint32_t cols_andn(uint32_t x, uint32_t m)
+{
+#if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
+    return bop3<0x20>(x, m, vconst<0x1FFu>());
+#else
+    return x & ~m & 0x1FFu;
+#endif
+}
+// The tables a pass can take: rule D's box -> row keep masks (lock_fill, 512
+// words) and rule C's box terms (col_fill, 512 half-words); each its own array
+struct PassTables {
+    const uint32_t *lock;
+    const uint16_t *col;
+};
 
 PS_FN uint32_t spread_rows(uint32_t c) { return c | (c << 10) | (c << 20); }  // 9-bit column set -> 3 rows
 PS_FN uint32_t guard_rows(uint32_t g) { return g - (g >> 9); }               // guard flags -> whole rows
@@ -328,18 +383,25 @@ PS_FN uint32_t rule_a(const Board &B, uint32_t (&single)[3])
 // with literal constants, three-input logic as v_bitop3_b32 on VGPRs, right
 // shifts only, 16-bit multiplies for 9-bit results, and one v_mul_u32_u24
 // per spread of a set over a band's three rows.  With rule A, 1797 VALU per
-// pass with SDK_PLANE_LC 3, 1602 with the table (profiles/isa_plane_pass.json).
+// pass with SDK_PLANE_LC 3, 1602 with the table, 1449 with the column table
+// as well (profiles/isa_plane_pass.json).
 // TBL: rule D's box -> row form from the table `tbl` (lock_fill) instead of
 // point_rows_apply -- the same planes (pass_body(B, nd, hall, tbl) below).
-template <bool TBL>
-PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3], const uint32_t *tbl)
+// COL 1: rule C's box terms from the table `ctbl` (col_fill) as well -- the
+// same planes again (pass_body_tables below).
+template <bool TBL, int COL = 0>
+PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3], const uint32_t *tbl,
+                           const uint16_t *ctbl = nullptr)
 {
+    static_assert(COL == 0 || (COL == 1 && SDK_PLANE_HX && (SDK_PLANE_LC & 1)), "the column table stands for vp");
+    // boxall's "box has a place" bits: bits 0/3/6, or where the table's entries hold them
+    constexpr uint32_t BM = COL ? (uint32_t)COL_BOXES : (uint32_t)BOXC;
     hall[0] = hall[1] = hall[2] = 0u;
 #if SDK_PLANE_GROUP > 1
     uint32_t hgrp[3] = {0u, 0u, 0u};
 #endif
     // per unit kind, "d has a place": row guard bits, columns, box bits 0/3/6
-    uint32_t rowall = GUARDS, colall = 0x1FFu, boxall = BOXC;
+    uint32_t rowall = GUARDS, colall = 0x1FFu, boxall = BM;
 #pragma unroll
     for (int d = 0; d < 9; ++d) {
         // hidden singles placed for digits < d this pass leave d's plane
@@ -366,9 +428,42 @@ PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3
         }
         // ---- C: hidden singles of d; units with no place left for d
         uint32_t o[3], t[3], gr[3], hb[3];
-#if SDK_PLANE_LC
         uint32_t vp[3];  // rule D: per band, the column of each box whose places lie in one column
+        (void)vp;
+        if constexpr (COL != 0) {
+            // the column patterns first: a digit's three lookups are in flight
+            // over the row tests here and the column folds below, which need
+            // o and t only
+            uint32_t off[3];
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const uint32_t y = B.P[d][b];
+                const uint32_t s1 = y >> 10, s2 = y >> 20;
+                o[b] = or3(y, s1, s2);
+                t[b] = maj3(y, s1, s2);
+                off[b] = col_offset(o[b]);
+            }
+#if SDK_PLANE_COLTBL_GROUP >= 2
+#pragma unroll
+            for (int b = 0; b < 3; ++b) PS_PIN(off[b]);
 #endif
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                vp[b] = col_read(ctbl, off[b]);  // the entry: vp and, above it, the box bits
+#if SDK_PLANE_COLTBL_GROUP == 1
+                PS_PIN(vp[b]);
+#endif
+            }
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const uint32_t y = B.P[d][b];
+                const uint32_t y1 = y + ROWS;
+                rowall &= y1;
+                const uint32_t z = y & y1;
+                const uint32_t nz = (z + ROWS) & GUARDS;
+                gr[b] = nz - (nz >> 9);
+            }
+        } else {
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
             const uint32_t y = B.P[d][b];
@@ -401,10 +496,27 @@ PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3
 #endif
 #endif
         }
+        }
         const uint32_t O = or3(o[0], o[1], o[2]);
         colall &= O;
         const uint32_t mo3 = maj3(o[0], o[1], o[2]);  // columns with places in >= 2 bands
-        const uint32_t hc = andn2(O, or3(t[0], t[1], t[2]), mo3) & 0x1FFu;
+        uint32_t hc = andn2(O, or3(t[0], t[1], t[2]), mo3) & 0x1FFu;
+        if constexpr (COL != 0) {
+#if SDK_PLANE_COLTBL_GROUP >= 3
+            // (pins are kept in order: the row tests and the column singles
+            // are made before the wait for the entries, not after it)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) PS_PIN(gr[b]);
+            PS_PIN(hc);
+#endif
+#if SDK_PLANE_COLTBL_GROUP >= 2
+#pragma unroll
+            for (int b = 0; b < 3; ++b) PS_PIN(vp[b]);
+#endif
+            boxall &= and3(vp[0], vp[1], vp[2]);
+#pragma unroll
+            for (int b = 0; b < 3; ++b) hb[b] = cols_andn(vp[b], t[b]);
+        }
 #if SDK_PLANE_HX
         // box and column singles share one spread over the band's rows
 #pragma unroll
@@ -423,7 +535,8 @@ PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3
         // cells in the other two bands lose d; likewise for a row
         // (point_rows).  The singles of d see it next pass.
         {
-            const uint32_t vpa = or3(vp[0], vp[1], vp[2]);
+            // (with the column table vp[] still carries the entries' box bits: masked off here, once)
+            const uint32_t vpa = COL ? or3(vp[0], vp[1], vp[2]) & 0x1FFu : or3(vp[0], vp[1], vp[2]);
             const uint32_t one_band = andn(xor3(o[0], o[1], o[2]), mo3) & 0x1FFu;  // columns with places in one band
             (void)vpa;
             (void)one_band;
@@ -527,7 +640,8 @@ PS_FN uint32_t pass_body_t(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3
     }
 #endif
     (void)tbl;
-    return or3(rowall ^ GUARDS, colall ^ 0x1FFu, (boxall & BOXC) ^ BOXC);
+    (void)ctbl;
+    return or3(rowall ^ GUARDS, colall ^ 0x1FFu, (boxall & BM) ^ BM);
 }
 PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3])
 {
@@ -537,13 +651,19 @@ PS_FN uint32_t pass_body(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3],
 {
     return pass_body_t<true>(B, nd, hall, tbl);
 }
+// with both tables (COL 1: rule C's box terms from T.col; COL 0: T.col is not read)
+template <int COL>
+PS_FN uint32_t pass_body_tables(Board &B, const uint32_t (&nd)[3], uint32_t (&hall)[3], const PassTables &T)
+{
+    return pass_body_t<true, COL>(B, nd, hall, T.lock, T.col);
+}
 
 // One propagation pass (rules A-D above), rule A first, on the state the
 // previous pass left.  Returns DEAD, SOLVED, STUCK (no single found: und[] =
 // the undetermined cells; rule D may still have removed places, which the
 // next pass sees) or OPEN (pass again).
-template <bool TBL>
-PS_FN int pass_t(Board &B, uint32_t und[3], const uint32_t *tbl)
+template <bool TBL, int COL = 0>
+PS_FN int pass_t(Board &B, uint32_t und[3], const uint32_t *tbl, const uint16_t *ctbl = nullptr)
 {
     uint32_t single[3], nd[3], hall[3];
     uint32_t dead = rule_a(B, single);
@@ -556,7 +676,7 @@ PS_FN int pass_t(Board &B, uint32_t und[3], const uint32_t *tbl)
     const bool all_single = and3(single[0], single[1], single[2]) == ROWS;
     const bool any_nd = or3(nd[0], nd[1], nd[2]) != 0;
     pin_board(B);
-    dead |= pass_body_t<TBL>(B, nd, hall, tbl);
+    dead |= pass_body_t<TBL, COL>(B, nd, hall, tbl, ctbl);
     if (dead) return DEAD;
     if (all_single) return SOLVED;
     const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
@@ -569,6 +689,9 @@ PS_FN int pass_t(Board &B, uint32_t und[3], const uint32_t *tbl)
 PS_FN int pass(Board &B, uint32_t und[3]) { return pass_t<false>(B, und, nullptr); }
 // the same pass with rule D's box -> row form from the table (lock_fill)
 PS_FN int pass(Board &B, uint32_t und[3], const uint32_t *tbl) { return pass_t<true>(B, und, tbl); }
+// with both tables (COL 1: rule C's box terms from T.col; COL 0: T.col is not read)
+template <int COL>
+PS_FN int pass_tables(Board &B, uint32_t und[3], const PassTables &T) { return pass_t<true, COL>(B, und, T.lock, T.col); }
 
 // The look-ahead pass: the same body, then rule A on the planes it leaves, so
 // the pass settles its own verdict instead of leaving it to the next one (a
@@ -580,13 +703,14 @@ PS_FN int pass(Board &B, uint32_t und[3], const uint32_t *tbl) { return pass_t<t
 // digit, or a cell is empty now; SOLVED: no cell was undetermined on entry
 // (this was the verifying pass); STUCK: no cell became determined and no
 // hidden single was placed; OPEN otherwise.
-template <bool TBL>
-PS_FN int pass_ahead_t(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const uint32_t *tbl)
+template <bool TBL, int COL = 0>
+PS_FN int pass_ahead_t(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const uint32_t *tbl,
+                       const uint16_t *ctbl = nullptr)
 {
     uint32_t single[3], hall[3];
     const bool all_single = or3(und[0], und[1], und[2]) == 0;
     pin_board(B);
-    uint32_t dead = pass_body_t<TBL>(B, nd, hall, tbl);
+    uint32_t dead = pass_body_t<TBL, COL>(B, nd, hall, tbl, ctbl);
     const bool newh = or3(hall[0] & und[0], hall[1] & und[1], hall[2] & und[2]) != 0;
     dead |= rule_a(B, single);
 #pragma unroll
@@ -607,6 +731,12 @@ PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3])
 PS_FN int pass_ahead(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const uint32_t *tbl)
 {
     return pass_ahead_t<true>(B, und, nd, tbl);
+}
+// with both tables (COL 1: rule C's box terms from T.col; COL 0: T.col is not read)
+template <int COL>
+PS_FN int pass_ahead_tables(Board &B, uint32_t (&und)[3], uint32_t (&nd)[3], const PassTables &T)
+{
+    return pass_ahead_t<true, COL>(B, und, nd, T.lock, T.col);
 }
 
 // The walk's branch cell among the undetermined cells: node.py:63-65 takes
