@@ -463,6 +463,104 @@ int sdk_logic_batch(const uint8_t *d_boards /* NULL ok */, const uint16_t *d_sta
                     uint16_t *d_marks /* n*81, NULL ok */, int64_t n,
                     void *d_scratch, size_t scratch_bytes, void *stream);
 
+/* The solving path of n states: every deduction, round by round (library
+ * extension, no reference counterpart).  State, start state
+ * (board ANDed with the pencil marks; d_boards NULL: empty boards, d_start
+ * NULL: masks of 0x1FF, both NULL refused), dead and solved are
+ * sdk_logic_batch's.  `rules` is one mask of SDK_LOGIC_N .. SDK_LOGIC_F4 that
+ * holds N; the nine CLASSES, in order, are its bit indices: 0 N, 1 H, 2 L,
+ * 3 S2, 4 S3, 5 S4, 6 F2, 7 F3, 8 F4.
+ * A FIRING is one of
+ *   a Hall firing (m, I, u): on matrix m (0..71, 9 kind + idx: kind 0 the row
+ *     fish of digit idx, rows x columns; 1 the column fish, columns x rows;
+ *     2..4 hidden in row / column / box idx, digits x cells; 5..7 naked in row
+ *     / column / box idx, cells x digits; the cells of a box row by row) a
+ *     k-subset I of rows (a row mask) with union u and |u| == k.  Its action:
+ *     u leaves every row outside I.  Class N is size 1 on the naked matrices
+ *     45..71 (a cell with one candidate d: d leaves the unit's other cells; a
+ *     single fires once per unit it lies in), class H size 1 on the hidden
+ *     matrices 18..44 (a digit with one place in a unit: the cell loses its
+ *     other digits), class S_k size k on 18..71, class F_k size k on 0..17;
+ *   an L firing (dir, d, line, box): line 0..8 a row, 9..17 a column, meeting
+ *     the box; digit d has a place in the three shared cells and, dir 0
+ *     (pointing), no other place in the box: d leaves the rest of the line;
+ *     dir 1 (claiming), no other place in the line: d leaves the rest of the
+ *     box.
+ * A firing is EFFECTIVE on a state when its action removes at least one
+ * candidate there; `removed` is how many.  A VIOLATION is a k-subset with
+ * |u| < k; the size-1 violations (an empty row of a matrix 18..71) are the
+ * rating's dead and are always checked, whatever `rules` is.
+ * The schedule of one board, r = 0 rounds done:
+ *   1 the state is dead: stop, SDK_PATH_DEAD, with one contradiction event:
+ *     class 0, round r + 1, removed 0, the smallest (m, I) among the matrices
+ *     18..71 with an empty row, u = 0;
+ *   2 the state is solved: stop, SDK_PATH_SOLVED;
+ *   3 max_rounds > 0 and r == max_rounds: stop, SDK_PATH_LIMITED;
+ *   4 the classes of `rules` in ascending order: an S_k or F_k with a
+ *     violation stops the board, SDK_PATH_DEAD, with a contradiction event of
+ *     that class, the smallest (m, I) and its u; the first class with an
+ *     effective firing is the round's class; no class fires: SDK_PATH_STUCK;
+ *   5 ++r; every effective firing of the round's class is one event of round
+ *     r, all evaluated on the round's start state; the new state is the start
+ *     state minus the union of their removals.
+ * (m, I) compares m first, then I as a number.  Every round removes a
+ * candidate: at most 648 rounds.  The end state is the fixpoint of `rules` on
+ * the start state, or dead (the rules are monotone), and the
+ * path uses no class above the lowest prefix of classes whose closure solves
+ * the board.  The events are covariant under every symmetry of the state.
+ *   row k of d_rows = four words, one 16-byte store a row:
+ *     word 0  the owner (the board's index);
+ *     word 1  round (bits 0..15), class (16..19), bit 20 set for a
+ *             contradiction event, removed (24..31);
+ *     word 2  a Hall event: m | I << 8 | u << 17; an L event: m = 72 + dir,
+ *             I = 1 << (d - 1), u = line | box << 5;
+ *     word 3  the candidates left over all 81 cells after the event's round;
+ *             for a contradiction event the count before the round.
+ * Rows [0, listed) are all written, without holes; nothing at or beyond row
+ * `listed` is written.  The ORDER of the rows is unspecified; the SET is
+ * reproducible.
+ *   d_info (DEVICE memory, 2 values) = {total, listed = min(total, capacity)};
+ *   rows beyond the capacity are dropped (which ones is unspecified) and the
+ *   call still returns 0.  capacity == 0 is a pure count (d_rows may be NULL).
+ *   d_count[i]      = board i's events, the contradiction event included,
+ *                     whatever the capacity;
+ *   d_rounds[i]     = the rounds done;
+ *   d_status[i]     = SDK_PATH_DEAD, SDK_PATH_SOLVED, SDK_PATH_STUCK or
+ *                     SDK_PATH_LIMITED; SDK_INVALID for a byte above 9 or a
+ *                     mark bit above 0x1FF: count 0, no rounds, no row;
+ *   d_hist[9 i + c] = the events of class c, contradiction events not counted;
+ *   d_marks[81 i+c] = the end state, all zero when DEAD or invalid.
+ * d_hist and d_marks may be NULL.  d_rows needs 16-byte alignment, d_info 8,
+ * d_count, d_rounds, d_status and d_hist 4, d_start and d_marks 2, d_boards
+ * none.  Inputs are never modified and no byte outside these extents is
+ * written.
+ * d_scratch: at least sdk_path_scratch_bytes(n, max_waves) bytes of device
+ * memory (64: the board head and the row cursor), 8-byte aligned, contents
+ * irrelevant: the call re-arms its heads itself on `stream`.  SINGLE-STREAM
+ * like a workspace; the solve workspace is not involved.  max_waves > 0 caps
+ * the kernel's grid (0: the device's waves at the kernel's occupancy); results
+ * never depend on it.  Asynchronous on `stream`: two launches ordered by the
+ * stream alone.  Returns 0 / -1 (HIP error) / -2 (bad arguments: a mask
+ * outside 0x1FF or without N, max_rounds, capacity or max_waves negative, a
+ * capacity above INT64_MAX / 16 (its bytes would not fit an int64), n
+ * negative or above 2^31 - 1, both inputs NULL, a NULL pointer that is
+ * required, a misaligned pointer, scratch too small), by return code only;
+ * arguments are checked before any launch and n == 0 returns 0 once the
+ * scalars are checked.  sdk_path_scratch_bytes returns 0 for bad arguments.
+ * Row arithmetic is 64-bit throughout; a list past 4 GiB is not yet tested. */
+#define SDK_PATH_DEAD 0
+#define SDK_PATH_SOLVED 1
+#define SDK_PATH_STUCK 2
+#define SDK_PATH_LIMITED 3
+size_t sdk_path_scratch_bytes(int64_t n, int max_waves);
+int sdk_path_batch(const uint8_t *d_boards /* NULL ok */, const uint16_t *d_start /* NULL ok */,
+                   uint32_t rules, int max_rounds, int64_t n,
+                   uint32_t *d_rows /* capacity*4, NULL ok iff capacity == 0 */, int64_t capacity,
+                   int32_t *d_count /* n */, int32_t *d_rounds /* n */, int32_t *d_status /* n */,
+                   int32_t *d_hist /* n*9, NULL ok */, uint16_t *d_marks /* n*81, NULL ok */,
+                   int64_t *d_info /* DEVICE, 2 values */,
+                   void *d_scratch, size_t scratch_bytes, int max_waves, void *stream);
+
 /* The exact candidates of n boards (library extension, no reference
  * counterpart).  A completion of a board is a valid Sudoku grid -- every row,
  * column and box holds 1..9 once -- that keeps the givens.

@@ -52,6 +52,8 @@ EXPORTS = (
     "sdk_rate_batch",
     "sdk_logic_scratch_bytes",
     "sdk_logic_batch",
+    "sdk_path_scratch_bytes",
+    "sdk_path_batch",
     "sdk_candidates_scratch_bytes",
     "sdk_candidates_batch",
     "sdk_minimize_scratch_bytes",
@@ -84,6 +86,10 @@ SDK_LOGIC_NOT_RUN = -2  # ... and the open / left count of a step past the ladde
 # ... its rules: naked singles, hidden singles, locked candidates, subsets of 2..4, fish of 2..4
 (SDK_LOGIC_N, SDK_LOGIC_H, SDK_LOGIC_L, SDK_LOGIC_S2, SDK_LOGIC_S3, SDK_LOGIC_S4, SDK_LOGIC_F2, SDK_LOGIC_F3,
  SDK_LOGIC_F4) = (1 << k for k in range(9))
+SDK_PATH_DEAD = 0     # sdk_path_batch: the state has no completion
+SDK_PATH_SOLVED = 1   # ... the rules solved it
+SDK_PATH_STUCK = 2    # ... no rule of the mask removes a candidate
+SDK_PATH_LIMITED = 3  # ... max_rounds rounds are done
 SDK_MIN_GREEDY = 0  # sdk_minimize_batch: erase givens turn by turn while one completion is left
 SDK_MIN_PROBE = 1   # ... or test every given alone against the input board
 SDK_EXACT_DONE = 1     # sdk_count_exact_batch: the count is exact
@@ -176,6 +182,10 @@ def load() -> ctypes.CDLL:
     L.sdk_logic_scratch_bytes.argtypes = [i64, i32]
     L.sdk_logic_batch.restype = i32
     L.sdk_logic_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, sz, vp]
+    L.sdk_path_scratch_bytes.restype = sz
+    L.sdk_path_scratch_bytes.argtypes = [i64, i32]
+    L.sdk_path_batch.restype = i32
+    L.sdk_path_batch.argtypes = [vp, vp, ctypes.c_uint32, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
     L.sdk_candidates_scratch_bytes.restype = sz
     L.sdk_candidates_scratch_bytes.argtypes = [i64, i32]
     L.sdk_candidates_batch.restype = i32

@@ -26,7 +26,8 @@ ROOT = os.path.dirname(_HERE)
 # its own like rate_kernels.hip, LLVM's defaults, §23; ua_kernels.hip, the
 # unavoidable sets of a grid, likewise, §24; hit_kernels.hip, the hitting
 # sets of a family of cell sets, likewise, §25; logic_kernels.hip, the named
-# techniques on the rating's closures, likewise, §26)
+# techniques on the rating's closures, likewise, §26; path_kernels.hip, the
+# solving path on logic.h's matrices, likewise, §27)
 # SDK_PLANE_SCHED: machine-scheduler strategy of the plane kernel's unit
 # (iterative-ilp measured +1.4 % over LLVM's default on one MI355X, same
 # registers; "default" = LLVM's own, for A/B builds)
@@ -55,7 +56,8 @@ def sources(sched: str = _SCHED):
             ("backdoor_kernels.hip", []),
             ("ua_kernels.hip", []),
             ("hit_kernels.hip", []),
-            ("logic_kernels.hip", []))
+            ("logic_kernels.hip", []),
+            ("path_kernels.hip", []))
 
 
 SRCS = sources()

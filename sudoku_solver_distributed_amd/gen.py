@@ -38,6 +38,11 @@
   sets, the smallest proper puzzles inside a puzzle and the {-d, +d}
   neighbours, by the GPU's hitting sets (BatchSolver.hitting_sets /
   sub_puzzles; library extension).
+* ``hint(boards)`` / ``explain(events)`` / ``apply_events(marks, events)`` /
+  ``technique_counts(boards)`` -- the easiest deductions available now, one
+  English line an event, the replay of events on pencil marks and the events
+  per technique, by the GPU's solving path (BatchSolver.path; library
+  extension).
 """
 from __future__ import annotations
 
@@ -267,6 +272,176 @@ def grade(boards, device=None) -> torch.Tensor:
 def grade_names(steps) -> List[str]:
     """GRADE_NAMES for grade()'s steps ("invalid" for SDK_INVALID)."""
     return [GRADE_NAMES[s] if 0 <= s < len(GRADE_NAMES) else "invalid" for s in torch.as_tensor(steps).cpu().tolist()]
+
+
+# ---- the solving path (BatchSolver.path, DESIGN.md §27)
+# what an event's class says: PATH_CLASS_NAMES[cls]
+PATH_CLASS_NAMES = ("naked single", "hidden single", "locked candidates", "pair", "triple", "quad", "X-wing", "swordfish",
+                    "jellyfish")
+_UNIT_KINDS = ("row", "column", "box")
+
+
+def path_class_names(classes) -> List[str]:
+    """PATH_CLASS_NAMES for the class column of BatchSolver.path's events."""
+    return [PATH_CLASS_NAMES[c] for c in torch.as_tensor(classes).cpu().tolist()]
+
+
+def hint(boards, start=None, rules: int = 0x1FF, device=None):
+    """The easiest deductions available now on every state: BatchSolver.path
+    with max_rounds=1, (events, offsets, status).  Every event of a state is
+    of one class, the lowest of `rules` that removes a candidate; a solved,
+    stuck or dead state has none (a dead one its contradiction event).
+    Library extension, no reference counterpart."""
+    return get_solver(device).path(boards, rules=rules, start=start, max_rounds=1)
+
+
+def technique_counts(boards, start=None, rules: int = 0x1FF, device=None) -> torch.Tensor:
+    """How many events of every class the solving path of every state holds:
+    an int32 (n, 9) device tensor (BatchSolver.path as a pure count), the
+    columns PATH_CLASS_NAMES.  Library extension, no reference counterpart."""
+    return get_solver(device).path(boards, rules=rules, start=start, capacity=0, return_hist=True)[-1]
+
+
+def _unit_cells(t: int, u: int) -> List[int]:
+    if t == 0:
+        return [9 * u + k for k in range(9)]
+    if t == 1:
+        return [9 * k + u for k in range(9)]
+    return [9 * (3 * (u // 3) + k // 3) + 3 * (u % 3) + k % 3 for k in range(9)]
+
+
+def _path_tables():
+    """(cell, digit) of element j of row i of matrix m, as two (72, 9, 9)
+    arrays, and the cells an L firing clears as a (2, 18, 9, 81) 0/1 array."""
+    cell = np.zeros((72, 9, 9), dtype=np.int64)
+    digit = np.zeros((72, 9, 9), dtype=np.int64)
+    for m in range(72):
+        kind, idx = divmod(m, 9)
+        for i in range(9):
+            for j in range(9):
+                if kind == 0:
+                    cell[m, i, j], digit[m, i, j] = 9 * i + j, idx
+                elif kind == 1:
+                    cell[m, i, j], digit[m, i, j] = 9 * j + i, idx
+                elif kind < 5:
+                    cell[m, i, j], digit[m, i, j] = _unit_cells(kind - 2, idx)[j], i
+                else:
+                    cell[m, i, j], digit[m, i, j] = _unit_cells(kind - 5, idx)[i], j
+    locked = np.zeros((2, 18, 9, 81), dtype=bool)
+    for line in range(18):
+        lc = set(_unit_cells(line // 9, line % 9))
+        for box in range(9):
+            bc = set(_unit_cells(2, box))
+            if len(lc & bc) == 3:
+                locked[0, line, box, sorted(lc - bc)] = True
+                locked[1, line, box, sorted(bc - lc)] = True
+    return cell, digit, locked
+
+
+_PATH_TABLES = None
+
+
+def apply_events(marks, events, offsets=None):
+    """Replay the actions of path events on pencil marks: a Hall event takes u
+    out of every row of its matrix outside I, an L event takes its digit out
+    of the rest of the line (pointing) or of the box (claiming); a
+    contradiction event does nothing.  The events alone say what leaves, not
+    the state they were found on.  marks: (81,) masks with the events of that
+    one state, or (n, 81) with the CSR offsets of BatchSolver.path.  Returns
+    the new marks, a tensor for a tensor and an array for an array; the
+    arithmetic is NumPy's, on the host."""
+    global _PATH_TABLES
+    if _PATH_TABLES is None:
+        _PATH_TABLES = _path_tables()
+    cell, digit, locked = _PATH_TABLES
+    as_tensor = isinstance(marks, torch.Tensor)
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    mk = to_np(marks)
+    out = mk.astype(np.int64).reshape(-1, 81) & 0xFFFF
+    ev = to_np(events).astype(np.int64).reshape(-1, 8)
+    if offsets is None:
+        owner = np.zeros(len(ev), dtype=np.int64)
+    else:
+        owner = np.repeat(np.arange(out.shape[0]), np.diff(to_np(offsets).astype(np.int64)))
+    live = ev[:, 7] == 0
+    ev, owner = ev[live], owner[live]
+    clear = np.zeros_like(out)
+    hall = ev[:, 2] < 72
+    h, ho = ev[hall], owner[hall]
+    bits = 1 << np.arange(9)
+    sel = (((h[:, 3, None] & bits) == 0)[:, :, None] & ((h[:, 4, None] & bits) != 0)[:, None, :])
+    e, i, j = np.nonzero(sel)
+    np.bitwise_or.at(clear, (ho[e], cell[h[e, 2], i, j]), 1 << digit[h[e, 2], i, j])
+    lk, lo = ev[~hall], owner[~hall]
+    where = locked[lk[:, 2] - 72, lk[:, 4] & 31, lk[:, 4] >> 5]  # (events, 81)
+    e, c = np.nonzero(where)
+    np.bitwise_or.at(clear, (lo[e], c), lk[e, 3])
+    out = (out & ~clear).astype(mk.dtype if mk.dtype.kind in "iu" else np.int64).reshape(mk.shape)
+    return torch.as_tensor(out, device=marks.device) if as_tensor else out
+
+
+def _digits_text(mask: int) -> str:
+    return "{" + ",".join(str(d + 1) for d in range(9) if mask >> d & 1) + "}"
+
+
+def _join(names) -> str:
+    names = [str(x) for x in names]
+    return names[0] if len(names) == 1 else ", ".join(names[:-1]) + " and " + names[-1]
+
+
+def _cells_text(t: int, u: int, mask: int) -> str:
+    """The cells `mask` of unit u of kind t, as the UI would name them."""
+    ks = [k for k in range(9) if mask >> k & 1]
+    if t == 0:
+        return ("columns " if len(ks) > 1 else "column ") + _join(k + 1 for k in ks)
+    if t == 1:
+        return ("rows " if len(ks) > 1 else "row ") + _join(k + 1 for k in ks)
+    return _join("r%dc%d" % (c // 9 + 1, c % 9 + 1) for c in (_unit_cells(2, u)[k] for k in ks))
+
+
+def explain(events) -> List[str]:
+    """One English line per event of BatchSolver.path, for example "naked
+    pair {3,7} in row 4, columns 2 and 5: 3 candidates leave"."""
+    lines = []
+    for rnd, cls, m, I, u, removed, left, contra in (
+            events.detach().cpu().numpy() if isinstance(events, torch.Tensor) else np.asarray(events)).reshape(-1, 8).tolist():
+        tail = ": %d candidate%s leave%s" % (removed, "" if removed == 1 else "s", "s" if removed == 1 else "")
+        if m >= 72:
+            d, line, box = I.bit_length(), u & 31, u >> 5
+            lname = "%s %d" % (_UNIT_KINDS[line // 9], line % 9 + 1)
+            if m == 72:
+                lines.append("pointing: %d in box %d lies in %s only%s %s" % (d, box + 1, lname, tail, lname))
+            else:
+                lines.append("claiming: %d in %s lies in box %d only%s box %d" % (d, lname, box + 1, tail, box + 1))
+            continue
+        kind, idx = divmod(m, 9)
+        size = bin(I).count("1")
+        if kind < 2:
+            lines_, cross = ("rows", "columns") if kind == 0 else ("columns", "rows")
+            what = "%s on %d in %s %s, %s %s" % (PATH_CLASS_NAMES[min(cls, 8)] if cls >= 6 else "fish", idx + 1, lines_,
+                                                 _join(k + 1 for k in range(9) if I >> k & 1), cross,
+                                                 _join(k + 1 for k in range(9) if u >> k & 1) if u else "none")
+        else:
+            t = (kind - 2) % 3
+            unit = "%s %d" % (_UNIT_KINDS[t], idx + 1)
+            hidden = kind < 5
+            digits, cells = (I, u) if hidden else (u, I)
+            where = _cells_text(t, idx, cells) if cells else "no cell"
+            if size == 1 and not contra:
+                what = "%s single %s in %s, %s" % ("hidden" if hidden else "naked", _digits_text(digits)[1:-1], unit, where)
+            else:
+                what = "%s %s %s in %s, %s" % ("hidden" if hidden else "naked", PATH_CLASS_NAMES[3 + min(size, 4) - 2] if size > 1
+                                               else "single", _digits_text(digits), unit, where)
+        if contra:
+            if size == 1 and kind >= 5:
+                lines.append("contradiction: %s, %s has no candidate" % (unit, where))
+            elif size == 1:
+                lines.append("contradiction: %s has no place for %s" % (unit, _digits_text(I)[1:-1]))
+            else:
+                lines.append("contradiction: %s -- %d rows share %d" % (what, size, bin(u).count("1")))
+        else:
+            lines.append(what + tail)
+    return lines
 
 
 def make_unique(boards, device=None):

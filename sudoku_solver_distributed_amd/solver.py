@@ -39,6 +39,10 @@ SUB_PUZZLES_MAX_ROWS = 1 << 28
 # the default ladder: singles, hidden singles, locked candidates, pairs, triples / quads, X-wing, swordfish / jellyfish
 N, H, L, S2, S3, S4, F2, F3, F4 = (1 << k for k in range(9))
 DEFAULT_LADDER = (N, N | H, N | H | L, N | H | L | S2, N | H | L | S2 | S3 | S4, N | H | L | S2 | S3 | S4 | F2, 0x1FF)
+ALL = 0x1FF
+# the columns of path's events and the names of its classes (the bit indices of a rule mask)
+PATH_COLUMNS = ("round", "cls", "m", "I", "u", "removed", "left", "contradiction")
+PATH_CLASSES = ("N", "H", "L", "S2", "S3", "S4", "F2", "F3", "F4")
 
 __all__ = [
     "BatchSolver", "get_solver", "as_boards", "SDK_SOLVED", "SDK_UNSOLVABLE",
@@ -152,6 +156,7 @@ class BatchSolver:
         self._canon_scratch = None  # canonical's scratch, likewise
         self._rate_scratch = None  # rate's scratch, likewise
         self._logic_scratch = None  # logic's scratch, likewise
+        self._path_scratch = None  # path's scratch, likewise
         self._cand_scratch = None  # candidates' scratch, likewise
         self._min_scratch = None  # minimize's scratch, likewise
         self._sample_scratch = None  # sample's scratch, likewise
@@ -518,6 +523,105 @@ class BatchSolver:
         self._rc_only(rc, "sdk_logic_batch")
         out = (step,) + ((opens,) if return_open else ()) + ((left,) if return_left else ()) + ((marks,) if return_marks else ())
         return out if len(out) > 1 else step
+
+    # ------------------------------------------------------- solving path
+    def path(self, boards=None, rules: int = 0x1FF, start=None, max_rounds: int = 0, capacity=None,
+             return_marks: bool = False, return_hist: bool = False, stream=None, max_waves: int = 0):
+        """Every deduction of every state, round by round (sdk_path_batch;
+        library extension, no reference counterpart; the definition is in
+        include/sudoku_hip.h and DESIGN.md §27) in CSR form: (events, offsets
+        (n + 1,) int64, status (n,) int32), state i's events being
+        events[offsets[i]:offsets[i + 1]].  rules: one mask of N .. F4 that
+        holds N; its bit indices are the classes 0 N, 1 H, 2 L, 3 S2, 4 S3,
+        5 S4, 6 F2, 7 F3, 8 F4.  Every round fires all effective deductions
+        of the easiest class that has one, on the round's start state, so the
+        path is deterministic, the same for every symmetry image and ends in
+        logic's fixpoint of `rules`.  events is an int32 (m, 8) tensor, the
+        columns PATH_COLUMNS: round, cls, m, I, u, removed, left,
+        contradiction -- (m, I, u) the matrix, the row mask and the union of
+        a Hall firing, or m = 72 + dir, I = 1 << (d - 1), u = line | box << 5
+        of a locked-candidates firing; removed the candidates the event takes
+        away, left those the state keeps after the event's round; a dead
+        state ends in one contradiction event (removed 0, left the count
+        before).  Events are sorted by (state, round, m, I, u): the result is
+        reproducible bit for bit.  status: SDK_PATH_DEAD 0, SDK_PATH_SOLVED 1,
+        SDK_PATH_STUCK 2 (no rule of the mask applies), SDK_PATH_LIMITED 3
+        (max_rounds > 0 rounds are done), SDK_INVALID for a byte > 9 or a
+        mark above 0x1FF (no events).  boards / start: logic's.  capacity:
+        rows of the raw list; None counts first and lists at the exact size,
+        an explicit one that overflows raises SudokuHipError with the number
+        to ask for; capacity=0 is a pure count (no events, all offsets 0).
+        return_marks: also the end states, int16 (n, 81), zero when dead;
+        return_hist: also int32 (n, 9), the events per class, contradiction
+        events not counted.  max_waves > 0 caps the kernel's
+        grid; results never depend on it.  SYNCHRONOUS on the stream (the
+        list's length comes back to the host); one cached scratch tensor
+        serves every call, ordered like the workspace's."""
+        rules, max_rounds = int(rules), int(max_rounds)
+        if rules & ~0x1FF or not rules & N:
+            raise ValueError("rules is a mask inside 0x1FF with N")
+        if max_rounds < 0 or int(max_waves) < 0:
+            raise ValueError("max_rounds and max_waves must be >= 0")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        if boards is None and start is None:
+            raise ValueError("path needs boards, start or both")
+        p = self._dev(as_boards(boards, max_value=255)) if boards is not None else None
+        s = None
+        if start is not None:
+            s = torch.as_tensor(start)
+            if s.dtype not in (torch.int16, torch.uint16):
+                s = s.to(torch.int16)
+            s = self._dev(s.reshape(-1, 81))
+        n = p.shape[0] if p is not None else s.shape[0]
+        if p is not None and s is not None and s.shape[0] != n:
+            raise ValueError("boards and start differ in length")
+        ctx = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        with torch.cuda.device(self.device), ctx():
+            count = torch.zeros(n, dtype=torch.int32, device=self.device)
+            rounds = torch.zeros(n, dtype=torch.int32, device=self.device)
+            status = torch.zeros(n, dtype=torch.int32, device=self.device)
+            hist = torch.zeros((n, 9), dtype=torch.int32, device=self.device) if return_hist else None
+            marks = torch.zeros((n, 81), dtype=torch.int16, device=self.device) if return_marks else None
+            info = torch.zeros(2, dtype=torch.int64, device=self.device)
+            cap = 0 if capacity is None else int(capacity)
+            listed = 0
+            rows = torch.empty((0, 4), dtype=torch.int32, device=self.device)
+            for attempt in range(2 if n else 0):
+                rows = torch.empty((cap, 4), dtype=torch.int32, device=self.device)
+                with self._lock:
+                    sc = self._scratch("_path_scratch", int(self.lib.sdk_path_scratch_bytes(n, int(max_waves))))
+                    rc = self.lib.sdk_path_batch(p.data_ptr() if p is not None else None,
+                                                 s.data_ptr() if s is not None else None, rules, max_rounds, n,
+                                                 rows.data_ptr() if cap else None, cap, count.data_ptr(), rounds.data_ptr(),
+                                                 status.data_ptr(), hist.data_ptr() if return_hist else None,
+                                                 marks.data_ptr() if return_marks else None, info.data_ptr(), sc.data_ptr(),
+                                                 sc.numel(), int(max_waves), self._ws_stream(stream))
+                self._rc_only(rc, "sdk_path_batch")
+                total, listed = (int(v) for v in info.tolist())
+                if listed == total:
+                    break
+                if capacity is not None and cap == 0:
+                    break  # a pure count
+                if capacity is not None:
+                    raise SudokuHipError(f"path: the list overflowed, {total} rows asked for a slot and the capacity is "
+                                         f"{cap} (call again with capacity={total})")
+                cap = total
+            w = rows[:listed].to(torch.int64) & 0xFFFFFFFF
+            owner, w1, w2, left = w[:, 0], w[:, 1], w[:, 2], w[:, 3]
+            rnd, m, row_mask, union = w1 & 0xFFFF, w2 & 0xFF, (w2 >> 8) & 0x1FF, (w2 >> 17) & 0x7FFF
+            if listed:
+                order = torch.sort((m << 24) | (row_mask << 15) | union, stable=True)[1]
+                order = order[torch.sort(((owner << 16) | rnd)[order], stable=True)[1]]
+            else:
+                order = torch.zeros(0, dtype=torch.int64, device=self.device)
+            events = torch.stack([rnd, (w1 >> 16) & 15, m, row_mask, union, (w1 >> 24) & 0xFF, left, (w1 >> 20) & 1],
+                                 dim=1)[order].to(torch.int32)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+            if listed:  # (a pure count lists nothing: the offsets stay zero)
+                offsets[1:] = torch.cumsum(count.to(torch.int64), dim=0)
+        out = (events, offsets, status) + ((marks,) if return_marks else ()) + ((hist,) if return_hist else ())
+        return out
 
     # ---------------------------------------------------- unavoidable sets
     @staticmethod
